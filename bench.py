@@ -8,7 +8,9 @@ One "step" pushes WAVES = 512 synthetic waveforms per GPU through BOTH training 
 so value = N_gpus * 512 * steps / wall_time = B / (t_CNN + t_GAN) of SURVEY section 8d.  Inputs (template bank, labels, event)
 are resident in HBM before the timed region; every optimizer step, BatchNorm update and dropout draw is inside it.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+K timed steps after W warm-up steps; ms_per_step in the line is the wall time of one timed step.  --dump-outputs writes what the last
+timed step computed to DIR/*.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare output for output.
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a
 rank; started plainly it launches `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a CHILD process
 before anything here touches the GPU, relays the child's output and exits with its code.  A rank whose world size differs from
@@ -38,6 +40,8 @@ WORKLOADS = {
 PEAK_F32_MFMA_TFLOPS = 157.3       # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, = 1/16 of the bf16 peak
 PEAK_HBM_TBS = 8.0                 # MI355X_MICROARCH.md: HBM3E spec peak
 PEAK_F64_VALU_TFLOPS = 78.6        # fp64 vector: half the guide's FP32 vector peak (157.3; the guide has no FP64 row; MI355X datasheet 78.6)
+DUMP_SAMPLE = 1 << 18              # --dump-outputs: elements kept of a larger weight tensor (the same seeded positions on every run)
+DUMP_LIMIT = 64 << 20              # --dump-outputs: bytes in all
 
 
 def pmc_traffic_per_launch(run_mix):
@@ -123,6 +127,33 @@ def cpu_baseline(n_pix, cnn_batch=256, gan_batch_max=512, seconds_budget=30.0):
                     'iterations fit %.0f s on this host (baseline only)' % (cnn_batch, gan_batch_max, bg, WARM + TIMED, seconds_budget)}
 
 
+def dump_outputs(out_dir, last, nets):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy, so that two builds can be compared output for output.
+      cnn_losses (calls, 5) / gan_losses (4,), float64: the return values of the step's train_on_batch loops (what the caller receives);
+      <model>_wNNN, float32: every weight of the CNN, the discriminator and the generator after the step (model.get_weights() order, BatchNormalization
+      moving statistics included).  A tensor of more than DUMP_SAMPLE elements is flattened and sampled at DUMP_SAMPLE distinct positions drawn
+      from default_rng(crc32 of its name): the same positions on every run.  Returns the file names."""
+    import zlib
+    import numpy as np
+    arrays = {'cnn_losses': np.asarray([[float(v) for v in c] for c in last['cnn_calls']], np.float64),
+              'gan_losses': np.asarray([float(v) for v in last['gan']], np.float64)}
+    for tag, model in (('pe', nets.signal_pe), ('discriminator', nets.signal_discriminator), ('generator', nets.generator)):
+        for k, w in enumerate(model.get_weights()):
+            name = '%s_w%03d' % (tag, k)
+            w = np.asarray(w, np.float32)
+            if w.size > DUMP_SAMPLE:
+                idx = np.random.default_rng(zlib.crc32(name.encode())).choice(w.size, DUMP_SAMPLE, replace=False)
+                w = w.reshape(-1)[np.sort(idx)]
+            arrays[name] = w
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
+
+
 def run_opt_in_child(cmd, env, timeout_s):
     """The opt-in bf16-split leg: the same bench command in a CHILD process (fresh GPU context), started only after the headline numbers of this
     process are final.  Whatever happens to it -- non-zero exit, device fault, hang (killed at timeout_s), garbage on stdout -- comes back as
@@ -181,9 +212,14 @@ def main():
     ap.add_argument('--opt-in', action='store_true', help='after the headline numbers are final, time the same K steps under the opt-in bf16-split conv math in a '
                                                           'CHILD process (its failure, hang or fault becomes opt_in.error; never part of value)')
     ap.add_argument('--no-opt-in', action='store_true', help='(accepted for old command lines; the extra leg is off unless --opt-in is given)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): its losses and the trained '
+                         'weights, larger tensors as a fixed seeded sample; at most 64 MB')
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -259,8 +295,8 @@ def main():
         # (refdefaults replays hipGraphs: every replay returns the step's losses through one device -> host read, as the eager loop does)
         # the return values of the three train_on_batch calls the loop prints (bbhMahoGANy.py:1165, :1292, :1296) are kept and checked after
         # the timed region: a launch that wrote garbage at these batch sizes must not score
-        for _ in range(WAVES // CNN_BATCH):
-            last['cnn'] = cnn_step()
+        last['cnn_calls'] = [cnn_step() for _ in range(WAVES // CNN_BATCH)]
+        last['cnn'] = last['cnn_calls'][-1]
         last['gan'] = gan_step()
 
     def barrier():
@@ -283,6 +319,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:         # before anything else runs a step: the weights are the last timed step's
+        dump_outputs(args.dump_outputs, last, nets)
     conv = ops.prof_collect(0); wgrad = ops.prof_collect(1); syn_in_step = ops.prof_collect(3); x3 = ops.prof_collect(2); wino = ops.prof_collect(5); wgwino = ops.prof_collect(6); wino2 = ops.prof_collect(7); wgwino2 = ops.prof_collect(8)
     last_losses = {'cnn [total, mc_loss, q_loss, mc_acc, q_acc]': [float(v) for v in last['cnn']],
                    'gan [sg_loss, sg_acc, sd_loss, sd_acc]': [float(v) for v in last['gan']]}

@@ -1,13 +1,16 @@
 """Keras `.h5` layout, CPU only: the dependency-free HDF5 subset (gennet_amd/h5lite.py) and the
 Keras 2.x model / weight file layout on top of it (gennet_amd/keras_io.py).
 
-The reader is pinned on the four real Keras files the reference ships (2_model_version/weight_version/*.hdf5) through the
-committed structure fixture tests/golden/keras_h5_golden.json (names, shapes, CRC32s -- made by tests/golden/make_h5_golden.py);
-those tests skip where /root/reference is absent (the GPU box).  Everything else runs anywhere.
+The reader is pinned on the four real Keras files the reference ships (2_model_version/weight_version/*.hdf5) through the committed
+structure fixture tests/golden/keras_h5_golden.json (names, shapes, CRC32s).  The files are committed under tests/golden/keras_h5/: the two
+weights-only files unchanged, the two full-model files reduced (<name>.gz: the raw data of their large float32 datasets zeroed, the regions
+in filled.json) and rebuilt here with fill_words; tests/golden/make_h5_golden.py writes all of it.  Everything runs anywhere.
 """
+import gzip
 import json
 import os
 import struct
+import zlib
 
 import numpy as np
 import pytest
@@ -15,9 +18,29 @@ import pytest
 from gennet_amd import h5lite
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference/2_model_version/weight_version'
+REF = os.path.join(ROOT, 'tests', 'golden', 'keras_h5')
 GOLD = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'keras_h5_golden.json')))
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason='reference data files are not on this machine')
+FILLED = json.load(open(os.path.join(REF, 'filled.json')))
+
+
+def fill_words(off, nbytes):
+    """What the zeroed regions of a reduced file are rebuilt with: float32 words holding their own byte offsets (as make_h5_golden.py)."""
+    return np.arange(off, off + nbytes, 4, dtype=np.int64).astype('<f4').tobytes()
+
+
+def keras_file(fn):
+    """(bytes of the Keras file fn, {dataset path: [shape, dtype, CRC32] it must read back}).  A file stored reduced is rebuilt with
+    fill_words in its zeroed regions: those datasets must read back the fill, every other one the original file's bytes."""
+    want = {k: list(v) for k, v in GOLD[fn]['datasets'].items()}
+    if fn not in FILLED:
+        return open(os.path.join(REF, fn), 'rb').read(), want
+    buf = bytearray(gzip.decompress(open(os.path.join(REF, fn + '.gz'), 'rb').read()))
+    for path, off, n in FILLED[fn]:
+        shape, dtype, _ = want[path]
+        assert dtype == 'float32' and 4 * int(np.prod(shape)) == n and buf[off:off + n] == bytes(n), path
+        buf[off:off + n] = fill_words(off, n)
+        want[path][2] = zlib.crc32(fill_words(off, n)) & 0xFFFFFFFF
+    return bytes(buf), want
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -142,23 +165,25 @@ def test_h5lite_rejects_what_it_does_not_implement():
 # ---------------------------------------------------------------------------------------------------------------------
 # the reference's real Keras files
 # ---------------------------------------------------------------------------------------------------------------------
-@needs_ref
 @pytest.mark.parametrize('fn', sorted(GOLD))
 def test_reader_on_real_keras_files(fn):
-    got = h5lite.dump_structure(os.path.join(REF, fn))
+    raw, want_datasets = keras_file(fn)
+    got = h5lite.dump_structure(raw)
     want = GOLD[fn]
+    assert len(raw) == want['file_bytes']
     assert got['groups'] == want['groups']
-    assert {k: list(v) for k, v in got['datasets'].items()} == want['datasets']
+    assert {k: list(v) for k, v in got['datasets'].items()} == want_datasets
     assert json.loads(json.dumps(got['attrs'])) == want['attrs']
 
 
-@needs_ref
-def test_load_model_on_a_real_keras_file():
+def test_load_model_on_a_real_keras_file(tmp_path):
     """keras.models.load_model on the reference's d_model.hdf5 (Keras 2.1.6, functional Model): same layers, every weight
     equal to the file's dataset, trainable flags, compile settings and Adam iteration count restored."""
     from gennet_amd.keras.models import load_model
     from gennet_amd import keras_io
-    path = os.path.join(REF, 'd_model.hdf5')
+    path = str(tmp_path / 'd_model.hdf5')
+    with open(path, 'wb') as fh:
+        fh.write(keras_file('d_model.hdf5')[0])
     m = load_model(path)
     want = GOLD['d_model.hdf5']
     layers = keras_io.top_layers(m)

@@ -169,6 +169,46 @@ def test_bench_gpus_n_spawns_n_ranks(monkeypatch):
     assert r.returncode == 2 and 'WORLD_SIZE' in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_last_steps_results(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's losses (float64) and the trained weights of the three models (float32), larger tensors
+    as the same seeded sample on every call, under 64 MB in all; --steps below 1 is refused before anything runs."""
+    import subprocess
+    import zlib
+    import bench
+    from gennet_amd import bbh
+    n_pix = 2048
+    nets = bbh.Nets()
+    nets.signal_pe, nets.signal_discriminator, nets.generator = bbh.signal_pe_model(n_pix), bbh.signal_discriminator_model(n_pix), bbh.generator_model(n_pix)
+    last = {'cnn_calls': [[0.5, 0.25, 0.25, 0.0, 1.0], [0.4, 0.2, 0.2, 0.0, 1.0]], 'gan': [0.7, 0.5, 0.6, 0.5]}
+    names = bench.dump_outputs(str(tmp_path / 'a'), last, nets)
+    assert bench.dump_outputs(str(tmp_path / 'b'), last, nets) == names
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == sorted(n + '.npy' for n in names) and 'cnn_losses.npy' in files and 'gan_losses.npy' in files
+    cnn = np.load(str(tmp_path / 'a' / 'cnn_losses.npy'))
+    assert cnn.dtype == np.float64 and np.array_equal(cnn, np.asarray(last['cnn_calls']))
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'gan_losses.npy')), np.asarray(last['gan']))
+    sampled = 0
+    for tag, m in (('pe', nets.signal_pe), ('discriminator', nets.signal_discriminator), ('generator', nets.generator)):
+        ws = m.get_weights()
+        assert len(ws) > 0 and all('%s_w%03d.npy' % (tag, k) in files for k in range(len(ws)))
+        for k, w in enumerate(ws):
+            a = np.load(str(tmp_path / 'a' / ('%s_w%03d.npy' % (tag, k))))
+            assert a.dtype == np.float32 and np.array_equal(a, np.load(str(tmp_path / 'b' / ('%s_w%03d.npy' % (tag, k)))))
+            if w.size <= bench.DUMP_SAMPLE:
+                assert np.array_equal(a, w)
+            else:
+                # the documented positions: DUMP_SAMPLE distinct flat indices from default_rng(crc32(name)), ascending
+                name = '%s_w%03d' % (tag, k)
+                idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(w.size, bench.DUMP_SAMPLE, replace=False))
+                assert np.unique(idx).size == bench.DUMP_SAMPLE and a.shape == (bench.DUMP_SAMPLE,)
+                assert np.array_equal(a, w.reshape(-1)[idx])
+                sampled += 1
+    assert sampled >= 5                                                           # the large conv and dense kernels
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) <= 64 << 20
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 2 and '--steps' in r.stderr
+
+
 def test_synth_host_helpers_match_reference_golden():
     from gennet_amd import templates as T
     for key, (M, alpha) in {'tukey_2184': (2184, 1 / 8.), 'tukey_4369': (4369, 1 / 8.), 'tukey_8738': (8738, 1 / 8.), 'tukey_64_half': (64, 0.5)}.items():
