@@ -72,6 +72,9 @@ _SIGS = {
     'gn_adam_step': [vp, vp, vp, vp, sz, f32, f32, f32, f32, vp],
     'gn_set_rng_base': [vp],
     'gn_adam_step_dyn': [vp, vp, vp, vp, sz, vp, f32, f32, f32, vp],
+    'gn_optim_step': [i32, vp, vp, vp, vp, vp, sz, f32, vp, f32, f32, f32, i32, vp, f32, vp],
+    'gn_optim_sumsq': [vp, sz, vp, vp],
+    'gn_optim_clip_factor': [vp, sz, f32, vp, vp],
     'gn_fill_normal_dyn': [vp, sz, f32, vp, u64, u64, vp],
     'gn_bn_finalize_zero_debias_dyn': [vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     'gn_prof_enable': [i32],
@@ -100,6 +103,7 @@ _SIZE_FNS = {
     'gn_dense_bwd_workspace': [i32, i32, i32],
     'gn_bn_stats_workspace': [sz, i32],
     'gn_conv1d_fwd_stats_workspace': [i32, i32, i32],
+    'gn_optim_sumsq_slots': [sz],
 }
 
 

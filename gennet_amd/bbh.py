@@ -19,7 +19,7 @@ import random as _pyrandom
 import numpy as np
 import torch
 
-from . import ops
+from . import engine, ops
 from .engine import Adam, Input, Model, Sequential, StepGraph, capturing, device, device_rng, to_device
 from .layers import (Activation, BatchNormalization, Conv1D, Conv2D, Dense, Dropout, Flatten, LeakyReLU, MaxPooling2D, MyLayer, ReLU,
                      Reshape, UpSampling1D)
@@ -165,11 +165,29 @@ def chisquare_loss(n_sig=1.0):
     return chisquare_Loss
 
 
-def build_and_compile(noise_signal, n_pix, lr=9e-5, do_pe=True, data_parallel=None, chi_loss=False, n_sig=1.0, filtsize=5, d_config=None):
+def optimizer_factory(name='adam', lr=9e-5, decay=0.0, clipnorm=None, clipvalue=None):
+    """Zero-argument factory of the optimizer every compiled model gets its own instance of: 'adam' is the reference's Adam(lr, beta_1=0.5)
+    (bbhMahoGANy.py:1101-1119), the others Keras' classes with their Keras defaults apart from lr (SGD(lr=lr): 2_model_version/no_weight_code/
+    noise_gan.py:75).  decay / clipnorm / clipvalue as in Keras (0 / None: off)."""
+    cls = {k.lower(): v for k, v in engine.OPTIMIZERS.items()}[name.lower()]
+    kw = dict(lr=lr, decay=decay)
+    if name.lower() == 'adam':
+        kw['beta_1'] = 0.5
+    if clipnorm:
+        kw['clipnorm'] = clipnorm
+    if clipvalue:
+        kw['clipvalue'] = clipvalue
+    return lambda: cls(**kw)
+
+
+def build_and_compile(noise_signal, n_pix, lr=9e-5, do_pe=True, data_parallel=None, chi_loss=False, n_sig=1.0, filtsize=5, d_config=None, optimizer=None):
     """bbhMahoGANy.py:1089-1119, in the reference's order (the order fixes which weights each compiled model trains):
     the combined model is compiled while the discriminator is frozen, the discriminator after it is unfrozen.
     chi_loss (:97, :1106-1109): the combined model trains on chisquare_Loss instead of binary cross-entropy; filtsize (:228): the generator's filter size; d_config (:424-426): the discriminator's
-    num_lays / batchnorm / maxpool."""
+    num_lays / batchnorm / maxpool.  optimizer: a zero-argument factory called once per compiled model (each Keras model owns its optimizer);
+    None is the reference's Adam(lr=lr, beta_1=0.5)."""
+    if optimizer is None:
+        optimizer = lambda: Adam(lr=lr, beta_1=0.5)     # noqa: E731
     nets = Nets()
     nets.generator = generator_model(n_pix, filtsize)
     nets.signal_discriminator = signal_discriminator_model(n_pix, **(d_config or {}))
@@ -177,15 +195,15 @@ def build_and_compile(noise_signal, n_pix, lr=9e-5, do_pe=True, data_parallel=No
     nets.signal_pe = signal_pe_model(n_pix) if do_pe else None
     dp = data_parallel
     nets.data_subtraction_on_generator = generator_after_subtracting_noise(nets.generator, nets.data_subtraction)
-    nets.data_subtraction_on_generator.compile(loss='binary_crossentropy', optimizer=Adam(lr=lr, beta_1=0.5), metrics=['accuracy'], data_parallel=dp)
+    nets.data_subtraction_on_generator.compile(loss='binary_crossentropy', optimizer=optimizer(), metrics=['accuracy'], data_parallel=dp)
     nets.signal_discriminator_on_generator = generator_containing_signal_discriminator(nets.data_subtraction_on_generator, nets.signal_discriminator)
     set_trainable(nets.signal_discriminator, False)
-    nets.signal_discriminator_on_generator.compile(loss=chisquare_loss(n_sig) if chi_loss else 'binary_crossentropy', optimizer=Adam(lr=lr, beta_1=0.5),
+    nets.signal_discriminator_on_generator.compile(loss=chisquare_loss(n_sig) if chi_loss else 'binary_crossentropy', optimizer=optimizer(),
                                                    metrics=['accuracy'], data_parallel=dp)
     set_trainable(nets.signal_discriminator, True)
-    nets.signal_discriminator.compile(loss='binary_crossentropy', optimizer=Adam(lr=lr, beta_1=0.5), metrics=['accuracy'], data_parallel=dp)
+    nets.signal_discriminator.compile(loss='binary_crossentropy', optimizer=optimizer(), metrics=['accuracy'], data_parallel=dp)
     if do_pe:
-        nets.signal_pe.compile(loss='mean_squared_error', optimizer=Adam(lr=lr, beta_1=0.5), metrics=['accuracy'], data_parallel=dp)
+        nets.signal_pe.compile(loss='mean_squared_error', optimizer=optimizer(), metrics=['accuracy'], data_parallel=dp)
     return nets
 
 

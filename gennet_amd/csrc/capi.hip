@@ -718,6 +718,30 @@ int gn_adam_step_dyn(float* p, const float* g, float* m, float* v, size_t n, con
   GN_REQUIRE(p && g && m && v && lr_t_dev, "adam_step_dyn: null pointer");
   return adam_step(p, g, m, v, n, 0.f, b1, b2, eps, (hipStream_t)stream, lr_t_dev);
 }
+int gn_optim_step(int rule, float* p, const float* g, float* s0, float* s1, float* s2, size_t n, float lr, const float* lr_dev, float h0, float h1,
+                  float eps, int nesterov, const float* clip_scale, float clipvalue, void* stream) {
+  GN_REQUIRE(rule >= GN_OPT_SGD && rule <= GN_OPT_AMSGRAD, "optim_step: unknown rule %d", rule);
+  if (!n) return GN_OK;
+  const int ns = rule == GN_OPT_AMSGRAD ? 3 : (rule == GN_OPT_ADADELTA || rule == GN_OPT_ADAMAX || rule == GN_OPT_ADAM) ? 2 : 1;
+  GN_REQUIRE(p && g && s0 && (ns < 2 || s1) && (ns < 3 || s2), "optim_step: null pointer (rule %d keeps %d state arrays)", rule, ns);
+  GN_REQUIRE(eps >= 0.f && clipvalue >= 0.f && h0 >= 0.f && h1 >= 0.f, "optim_step: negative hyper-parameter");
+  GN_REQUIRE(rule == GN_OPT_SGD || rule == GN_OPT_ADAGRAD || h0 <= 1.f, "optim_step: rho / beta_1 %g outside [0, 1]", h0);
+  GN_REQUIRE((rule != GN_OPT_ADAMAX && rule != GN_OPT_ADAM && rule != GN_OPT_AMSGRAD) || h1 <= 1.f, "optim_step: beta_2 %g outside [0, 1]", h1);
+  OptArgs a = {};
+  a.p = p; a.g = g; a.s0 = s0; a.s1 = ns > 1 ? s1 : nullptr; a.s2 = ns > 2 ? s2 : nullptr; a.n = n;
+  a.lr = lr; a.lr_dev = lr_dev; a.h0 = h0; a.h1 = h1; a.eps = eps; a.nesterov = nesterov ? 1 : 0; a.clip_scale = clip_scale; a.clipvalue = clipvalue;
+  return optim_step(rule, a, (hipStream_t)stream);
+}
+size_t gn_optim_sumsq_slots(size_t n) { return optim_sumsq_slots(n); }
+int gn_optim_sumsq(const float* g, size_t n, double* partials, void* stream) {
+  GN_REQUIRE(partials && (g || !n), "optim_sumsq: null pointer");
+  return optim_sumsq(g, n, partials, (hipStream_t)stream);
+}
+int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, void* stream) {
+  GN_REQUIRE(partials && factor && count > 0, "optim_clip_factor: null pointer or no partials");
+  GN_REQUIRE(clipnorm > 0.f, "optim_clip_factor: clipnorm %g must be > 0", clipnorm);
+  return optim_clip_factor(partials, count, clipnorm, factor, (hipStream_t)stream);
+}
 int gn_fill_normal_dyn(float* out, size_t n, float mean, const float* sd_dev, uint64_t seed, uint64_t offset, void* stream) {
   GN_REQUIRE(out && sd_dev, "fill_normal_dyn: null pointer");
   return fill_normal(out, n, mean, 0.f, seed, offset, (hipStream_t)stream, sd_dev);

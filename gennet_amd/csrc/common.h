@@ -201,6 +201,22 @@ int bn_bwd_apply(const float* dy, const float* y, const float* x, const uint8_t*
                  int act, float p, float rate, const float* scale, const float* shift, hipStream_t s, const LazyDy* lz = nullptr);
 int loss_run(int kind, const float* p, const float* y, float* dp, float* out, int B, int Bglobal, hipStream_t s);
 int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, hipStream_t s, const float* lr_t_dev = nullptr);
+// optim.hip
+struct OptArgs {
+  float *p, *s0, *s1, *s2;      // parameters and up to three state arrays (the rule's own: m | a | a, d | m, u | m, v | m, v, vhat)
+  const float* g;
+  size_t n;
+  float lr;                     // lr_eff or lr_t of this step, unless lr_dev is set (captured step: read at run time)
+  const float* lr_dev;
+  float h0, h1, eps;            // momentum | rho | beta_1, beta_2
+  int nesterov;
+  const float* clip_scale;      // clipnorm / norm (or 1) in device memory; null: no clip norm
+  float clipvalue;              // > 0: clip g to [-clipvalue, clipvalue] after the clip-norm scale
+};
+int optim_step(int rule, const OptArgs& a, hipStream_t s);
+size_t optim_sumsq_slots(size_t n);
+int optim_sumsq(const float* g, size_t n, double* partials, hipStream_t s);
+int optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, hipStream_t s);
 int transpose_w(const float* w, float* wt, int k, int Cin, int Cout, hipStream_t s);
 int conv2d_w2_fold(const float* w, const float* bias, float* wf, float* bf, int kh, int Cin, int Cout, hipStream_t s);
 int conv2d_w2_unfold(const float* dwf, const float* dbf, float* dw, float* db, int kh, int Cin, int Cout, hipStream_t s);
@@ -208,6 +224,13 @@ int up2_fold(const float* w, const float* bias, float* wf, float* bf, int Cin, i
 int up2_unfold(const float* dwf, const float* dbf, float* dw, float* db, int Cin, int Cout, int stride, hipStream_t s);
 
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+// grid of the streaming (HBM-bound) grid-stride kernels: one thread per item up to ~8 blocks of 256 per CU
+static inline unsigned stream_grid(size_t n_items, int block = 256) {
+  size_t g = (n_items + block - 1) / block;
+  if (g > 256 * 8) g = 256 * 8;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
 
 // Opt a kernel in to up to 160 KiB of dynamic LDS, once per DEVICE (the attribute is per device and function; `done` is the
 // call site's bit mask of devices already served, so a process that drives several GPUs stays correct).

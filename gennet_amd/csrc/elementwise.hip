@@ -4,13 +4,6 @@
 
 namespace gn {
 
-static inline unsigned stream_grid(size_t n_items, int block = 256) {
-  size_t g = (n_items + block - 1) / block;
-  if (g > 256 * 8) g = 256 * 8;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
 // ---------------------------------------------------------------------------------------------
 // activations
 // ---------------------------------------------------------------------------------------------

@@ -483,71 +483,281 @@ class Node(object):
 # --------------------------------------------------------------------------------------------------------------
 # optimizer
 # --------------------------------------------------------------------------------------------------------------
-class Adam(object):
-    """keras.optimizers.Adam: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); p -= lr_t*m/(sqrt(v)+eps)."""
+def _f32(x):
+    return float(np.float32(x))
 
-    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, **kwargs):
-        # float32 variables in Keras (K.variable): the values that take part -- and that Keras writes into training_config -- are the
-        # float32-rounded ones (the reference's own d_model.hdf5 records beta_2 = 0.9990000128746033); epsilon stays a python float
-        self.lr, self.beta_1, self.beta_2 = (float(np.float32(x)) for x in (lr, beta_1, beta_2))
-        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
-        if decay:
-            raise NotImplementedError('Adam(decay != 0) is not on the BBH hot path')
+
+class Optimizer(object):
+    """Keras 2.2.4 optimizer (keras/optimizers.py), the work every rule shares: the flat segments of the trained weights and the rule's state
+    per segment, the step's one varying scalar (eager: by value; inside a captured step graph: a StepGraph slot), Keras' gradient clipping
+    over all trained weights of the compiled model (clipnorm, then clipvalue), get_config, and the rule's optimizer_weights layout in .h5 files.
+    A subclass names its fused-pass rule (ops.OPT_RULES), its state arrays, its hyper-parameters and its per-step scalar.
+
+    Shared rules: iterations counts steps; decay > 0 gives lr_eff = lr / (1 + decay * iterations) with iterations before this step's
+    increment, t = iterations + 1; epsilon=None is 1e-7; what Keras holds as K.variable (lr, decay, momentum, RMSprop's rho, the betas) is
+    float32-rounded, the rest stays a python value.  The host computes the step scalar in fp64 and it is rounded once to fp32."""
+    RULE = None                            # ops.OPT_RULES key of the fused update
+    SLOTS = ()                             # per-weight state arrays, in the order of Keras' optimizer.weights
+    SAVES_ITERATIONS = True                # Keras 2.2.4 puts `iterations` first in optimizer.weights (SGD, Adamax, Adam; not RMSprop, Adagrad, Adadelta)
+    CONFIG = ()                            # get_config keys after 'lr', Keras' order
+
+    def __init__(self, lr, decay=0.0, clipnorm=None, clipvalue=None, **kwargs):
+        if kwargs:                         # keras.optimizers.Optimizer: only clipnorm / clipvalue
+            raise TypeError('Unexpected keyword argument passed to optimizer: %s' % sorted(kwargs)[0])
+        self.lr, self.decay = _f32(lr), _f32(decay)
+        self.clipnorm, self.clipvalue = clipnorm, clipvalue
         self.iterations = 0
-        self.state = None                  # [(group, start, stop, m, v)]
+        self.state = None                  # [(group, start, stop, [state tensor per slot])]
+
+    # -- what a rule defines
+    def _n_slots(self):
+        return len(self.SLOTS)
+
+    def _hyper(self):
+        """(h0, h1, eps, nesterov) of gn_optim_step."""
+        return 0.0, 0.0, 0.0, False
+
+    def _lr_eff(self, it):
+        return self.lr / (1.0 + self.decay * it) if self.decay > 0 else self.lr
+
+    def _scalar(self, it):
+        """The step's one varying value for the step that starts at iterations = it: lr_eff (lr_t for Adam, Adamax)."""
+        return self._lr_eff(it)
+
+    def _layout(self):
+        """Keras' optimizer.weights after `iterations`: one block of per-weight arrays per entry, the state slot it holds (None: a (1,) zero stub)."""
+        return list(range(self._n_slots()))
+
+    # -- shared work
+    def get_config(self):
+        cfg = {'lr': self.lr}
+        cfg.update((k, getattr(self, k)) for k in self.CONFIG)
+        if self.clipnorm is not None:
+            cfg['clipnorm'] = self.clipnorm
+        if self.clipvalue is not None:
+            cfg['clipvalue'] = self.clipvalue
+        return cfg
 
     def bind(self, params):
         self.state = []
         for grp, a, b in segments(params):
-            n = b - a
-            self.state.append((grp, a, b, torch.zeros(n, dtype=torch.float32, device=device()), torch.zeros(n, dtype=torch.float32, device=device())))
+            self.state.append((grp, a, b, [torch.zeros(b - a, dtype=torch.float32, device=device()) for _ in range(self._n_slots())]))
+        self._partials = self._factor = None
+        if self.clipnorm is not None and self.clipnorm > 0:
+            # owned here, not taken from ops.workspace: a captured step graph keeps these addresses for its whole life
+            self._part_slices, off = [], 0
+            for _, a, b, _ in self.state:
+                k = ops.optim_sumsq_slots(b - a)
+                self._part_slices.append((off, k)); off += k
+            self._partials = torch.zeros(off, dtype=torch.float64, device=device())
+            self._factor = torch.ones(1, dtype=torch.float32, device=device())
 
-    def _next_lr_t(self):
-        self.iterations += 1
-        t = self.iterations
-        return self.lr * np.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+    def _next_scalar(self):
+        it = self.iterations
+        self.iterations = it + 1
+        return self._scalar(it)
+
+    def _clip_scale(self):
+        if self._partials is None:
+            return None
+        for (grp, a, b, _), (o, k) in zip(self.state, self._part_slices):
+            ops.optim_sumsq(grp.grad[a:b], self._partials[o:o + k])
+        ops.optim_clip_factor(self._partials, self.clipnorm, self._factor)
+        return self._factor
+
+    def _update(self, p, g, st, lr, clip):
+        h0, h1, eps, nesterov = self._hyper()
+        ops.optim_step(self.RULE, p, g, st, lr, h0, h1, eps, nesterov, clip, self.clipvalue if self.clipvalue and self.clipvalue > 0 else 0.0)
 
     def step(self):
         cap = capturing()
-        # inside a captured step graph the iteration count advances once per REPLAY and lr_t reaches the kernel through device memory
-        lr_t = self._next_lr_t() if cap is None else cap.slot('f', self._next_lr_t)
-        for grp, a, b, m, v in self.state:
-            ops.adam_step(grp.data[a:b], grp.grad[a:b], m, v, lr_t, self.beta_1, self.beta_2, self.epsilon)
+        # inside a captured step graph the iteration count advances once per REPLAY and the scalar reaches the kernel through device memory
+        lr = self._next_scalar() if cap is None else cap.slot('f', self._next_scalar)
+        clip = self._clip_scale()
+        for grp, a, b, st in self.state:
+            self._update(grp.data[a:b], grp.grad[a:b], st, lr, clip)
 
-    def _moment_views(self, p):
-        for grp, a, b, m, v in self.state:
+    def _views(self, p):
+        for grp, a, b, st in self.state:
             if grp is p.group and a <= p.offset and p.offset + p.size <= b:
-                return m[p.offset - a:p.offset - a + p.size], v[p.offset - a:p.offset - a + p.size]
+                return [t[p.offset - a:p.offset - a + p.size] for t in st]
         raise KeyError('%s is not trained by this optimizer' % p.name)
 
-    def param_moments(self, params):
-        """[(m, v)] numpy arrays in the parameters' shapes (keras optimizer_weights order is decided by the caller)."""
-        out = []
-        for p in params:
-            m, v = self._moment_views(p)
-            out.append((m.cpu().numpy().reshape(p.shape), v.cpu().numpy().reshape(p.shape)))
+    def get_keras_weights(self, params):
+        """Keras' optimizer.get_weights() for trained weights `params` in model.trainable_weights order (the .h5 optimizer_weights)."""
+        out = [np.asarray(self.iterations, np.int64)] if self.SAVES_ITERATIONS else []
+        views = [self._views(p) for p in params]
+        for k in self._layout():
+            out += [np.zeros((1,), np.float32) if k is None else v[k].cpu().numpy().reshape(p.shape) for p, v in zip(params, views)]
         return out
 
-    def set_param_moments(self, params, moments):
-        for p, (mn, vn) in zip(params, moments):
-            m, v = self._moment_views(p)
-            m.copy_(to_device(np.asarray(mn, np.float32).reshape(-1))); v.copy_(to_device(np.asarray(vn, np.float32).reshape(-1)))
+    def split_keras_weights(self, vals, n):
+        """(iterations or None, [[n arrays] per block of _layout()]) from optimizer_weights in weight_names order (never by name: the scope
+        prefix depends on the Keras session).  Trailing stub blocks may be absent (Keras before amsgrad wrote no vhat)."""
+        vals = list(vals)
+        it = None
+        if self.SAVES_ITERATIONS:
+            if not vals or np.asarray(vals[0]).size != 1:
+                raise ValueError('%s: optimizer_weights do not start with the iteration count' % type(self).__name__)
+            it = int(np.asarray(vals[0]).reshape(-1)[0])
+            vals = vals[1:]
+        lay = self._layout()
+        need = len(lay)
+        while need and lay[need - 1] is None:
+            need -= 1
+        if len(vals) not in (need * n, len(lay) * n):
+            raise ValueError('%s: %d optimizer arrays for %d trained weights (layout %s)' % (type(self).__name__, len(vals), n, lay))
+        return it, [vals[j * n:(j + 1) * n] for j in range(len(vals) // n if n else 0)]
+
+    def set_keras_weights(self, params, vals):
+        it, blocks = self.split_keras_weights(vals, len(params))
+        views = [self._views(p) for p in params]
+        for k, arrs in zip(self._layout(), blocks):
+            if k is None:
+                continue
+            for p, v, a in zip(params, views, arrs):
+                a = np.asarray(a, np.float32)
+                if a.size != p.size:
+                    raise ValueError('%s: optimizer array of shape %s for %s %s' % (type(self).__name__, a.shape, p.name, p.shape))
+                v[k].copy_(to_device(a.reshape(-1)))
+        if it is not None:
+            self.iterations = it
 
     def get_state(self):
-        return {'iterations': self.iterations, 'mv': [(m.cpu().numpy(), v.cpu().numpy()) for _, _, _, m, v in (self.state or [])],
-                'config': (self.lr, self.beta_1, self.beta_2, self.epsilon)}
+        return {'iterations': self.iterations, 'slots': [[t.cpu().numpy() for t in st] for _, _, _, st in (self.state or [])],
+                'config': self.get_config()}
 
     def set_state(self, st):
         self.iterations = st['iterations']
-        for (_, _, _, m, v), (mn, vn) in zip(self.state, st['mv']):
-            m.copy_(to_device(mn)); v.copy_(to_device(vn))
+        for (_, _, _, ts), arrs in zip(self.state, st['slots']):
+            for t, a in zip(ts, arrs):
+                t.copy_(to_device(a))
+
+
+class SGD(Optimizer):
+    """keras.optimizers.SGD: v = momentum m - lr_eff g; m = v; p += momentum v - lr_eff g (nesterov) | v.  optimizer.weights: [iterations] + m
+    (the reference's g_model.hdf5 was compiled with SGD; 2_model_version/no_weight_code/noise_gan.py:75 trains with SGD(lr=lr))."""
+    RULE, SLOTS, CONFIG = 'sgd', ('m',), ('momentum', 'decay', 'nesterov')
+
+    def __init__(self, lr=0.01, momentum=0.0, decay=0.0, nesterov=False, **kwargs):
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.momentum, self.nesterov = _f32(momentum), bool(nesterov)
+
+    def _hyper(self):
+        return self.momentum, 0.0, 0.0, self.nesterov
+
+
+class RMSprop(Optimizer):
+    """keras.optimizers.RMSprop: a = rho a + (1 - rho) g^2; p -= lr_eff g / (sqrt(a) + eps).  optimizer.weights: a (no iterations)."""
+    RULE, SLOTS, SAVES_ITERATIONS, CONFIG = 'rmsprop', ('a',), False, ('rho', 'decay', 'epsilon')
+
+    def __init__(self, lr=0.001, rho=0.9, epsilon=None, decay=0.0, **kwargs):
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.rho = _f32(rho)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def _hyper(self):
+        return self.rho, 0.0, self.epsilon, False
+
+
+class Adagrad(Optimizer):
+    """keras.optimizers.Adagrad: a += g^2; p -= lr_eff g / (sqrt(a) + eps).  optimizer.weights: a (no iterations)."""
+    RULE, SLOTS, SAVES_ITERATIONS, CONFIG = 'adagrad', ('a',), False, ('decay', 'epsilon')
+
+    def __init__(self, lr=0.01, epsilon=None, decay=0.0, **kwargs):
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def _hyper(self):
+        return 0.0, 0.0, self.epsilon, False
+
+
+class Adadelta(Optimizer):
+    """keras.optimizers.Adadelta: a = rho a + (1 - rho) g^2; u = g sqrt(d + eps) / sqrt(a + eps); p -= lr_eff u; d = rho d + (1 - rho) u^2.
+    rho is a python float in Keras 2.2.4 (not a K.variable).  optimizer.weights: a + d (no iterations)."""
+    RULE, SLOTS, SAVES_ITERATIONS, CONFIG = 'adadelta', ('a', 'd'), False, ('rho', 'decay', 'epsilon')
+
+    def __init__(self, lr=1.0, rho=0.95, epsilon=None, decay=0.0, **kwargs):
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.rho = float(rho)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def _hyper(self):
+        return self.rho, 0.0, self.epsilon, False
+
+
+class Adamax(Optimizer):
+    """keras.optimizers.Adamax: lr_t = lr_eff / (1 - b1^t); m = b1 m + (1 - b1) g; u = max(b2 u, |g|); p -= lr_t m / (u + eps).
+    optimizer.weights: [iterations] + m + u."""
+    RULE, SLOTS, CONFIG = 'adamax', ('m', 'u'), ('beta_1', 'beta_2', 'decay', 'epsilon')
+
+    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, **kwargs):
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.beta_1, self.beta_2 = _f32(beta_1), _f32(beta_2)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+
+    def _hyper(self):
+        return self.beta_1, self.beta_2, self.epsilon, False
+
+    def _scalar(self, it):
+        return self._lr_eff(it) / (1.0 - self.beta_1 ** (it + 1))
+
+
+class Adam(Optimizer):
+    """keras.optimizers.Adam: lr_t = lr_eff*sqrt(1-b2^t)/(1-b1^t); p -= lr_t*m/(sqrt(v)+eps); amsgrad: vhat = max(vhat, v)
+    replaces v under the root.  optimizer.weights: [iterations] + m + v + vhat ((1,) zero stubs without amsgrad).  Without decay, amsgrad and
+    clipping the update is the library's original Adam pass (gn_adam_step), bit for bit."""
+    RULE, SLOTS, CONFIG = 'adam', ('m', 'v', 'vhat'), ('beta_1', 'beta_2', 'decay', 'epsilon', 'amsgrad')
+
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, amsgrad=False, **kwargs):
+        # float32 variables in Keras (K.variable): the values that take part -- and that Keras writes into training_config -- are the
+        # float32-rounded ones (the reference's own d_model.hdf5 records beta_2 = 0.9990000128746033); epsilon stays a python float
+        Optimizer.__init__(self, lr, decay, **kwargs)
+        self.beta_1, self.beta_2 = _f32(beta_1), _f32(beta_2)
+        self.epsilon = 1e-7 if epsilon is None else float(epsilon)
+        self.amsgrad = bool(amsgrad)
+
+    def _n_slots(self):
+        return 3 if self.amsgrad else 2
+
+    def _layout(self):
+        return [0, 1, 2 if self.amsgrad else None]
+
+    def _hyper(self):
+        return self.beta_1, self.beta_2, self.epsilon, False
+
+    def _scalar(self, it):
+        t = it + 1
+        return self._lr_eff(it) * np.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+
+    def _default_pass(self):
+        return not self.amsgrad and not self.decay > 0 and not (self.clipnorm and self.clipnorm > 0) and not (self.clipvalue and self.clipvalue > 0)
+
+    def _update(self, p, g, st, lr, clip):
+        if self._default_pass():
+            ops.adam_step(p, g, st[0], st[1], lr, self.beta_1, self.beta_2, self.epsilon)
+        else:
+            ops.optim_step('amsgrad' if self.amsgrad else 'adam', p, g, st, lr, self.beta_1, self.beta_2, self.epsilon, False, clip,
+                           self.clipvalue if self.clipvalue and self.clipvalue > 0 else 0.0)
+
+
+OPTIMIZERS = {'SGD': SGD, 'RMSprop': RMSprop, 'Adagrad': Adagrad, 'Adadelta': Adadelta, 'Adamax': Adamax, 'Adam': Adam}
+
+
+def optimizer_from_config(oc):
+    """keras.optimizers.deserialize of a training_config's optimizer_config {'class_name', 'config'}."""
+    cls = OPTIMIZERS.get(oc['class_name'])
+    if cls is None:
+        raise NotImplementedError('optimizer %s (supported: %s)' % (oc['class_name'], ', '.join(sorted(OPTIMIZERS))))
+    return cls(**oc['config'])
 
 
 def _get_optimizer(opt):
     if isinstance(opt, str):
-        if opt.lower() == 'adam':
-            return Adam()
-        raise NotImplementedError('optimizer %r' % opt)
+        cls = {k.lower(): v for k, v in OPTIMIZERS.items()}.get(opt.lower())
+        if cls is None:
+            raise NotImplementedError('optimizer %r' % opt)
+        return cls()
     return opt
 
 
@@ -837,13 +1047,13 @@ class Model(Layer):
             self.optimizer.bind(self._train_params)
             self._bound = True
             pend = getattr(self, '_pending_optimizer_weights', None)
-            if pend is not None:           # optimizer_weights of a loaded .h5: [iterations, m..., v..., (vhat stubs...)]
+            if pend is not None:           # optimizer_weights of a loaded .h5, in the layout of the optimizer's class (Optimizer._layout)
                 self._pending_optimizer_weights = None
-                order = self._keras_train_order()
-                n = len(order)
-                if len(pend) >= 1 + 2 * n:
-                    self.optimizer.iterations = int(np.asarray(pend[0]).reshape(-1)[0])
-                    self.optimizer.set_param_moments(order, list(zip(pend[1:1 + n], pend[1 + n:1 + 2 * n])))
+                try:
+                    self.optimizer.set_keras_weights(self._keras_train_order(), pend)
+                except ValueError as e:    # keras.models.load_model: warns and goes on without the optimizer state
+                    import warnings
+                    warnings.warn('optimizer state not loaded: %s' % e)
 
     def _keras_train_order(self):
         """The compiled trainable weights in keras' model.trainable_weights order (the order of optimizer_weights in .h5 files)."""

@@ -7,7 +7,7 @@
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
     from gennet_amd.keras.engine.topology import Layer
-    from gennet_amd.keras.optimizers import Adam
+    from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
 Every class executes on the HIP kernel library; see INTEGRATION.md.
 
@@ -51,7 +51,7 @@ for _d in (_core, _norm, _conv, _act):
 
 _TREE = {
     'models': _pick(_engine, 'Model', 'Sequential', 'load_model', 'model_from_json'),
-    'optimizers': dict(_pick(_engine, 'Adam'), **_unused('43', 'RMSprop', 'Adagrad', 'Adadelta', 'Adamax', 'Nadam')),
+    'optimizers': dict(_pick(_engine, 'Adam', 'SGD', 'RMSprop', 'Adagrad', 'Adadelta', 'Adamax'), **_unused('43', 'Nadam')),
     'engine': {},
     'engine.topology': _pick(_engine, 'Layer'),
     'layers': _top,

@@ -8,7 +8,9 @@ Layout (keras/engine/saving.py of Keras 2.2.4, restated; confirmed on the real K
                  weight_names [S] and one dataset per weight named by the weight ('dense_1/kernel:0' -> nested group);
   model file   : root attrs keras_version, backend, model_config (JSON), training_config (JSON);
                  group model_weights (as above); group optimizer_weights (attr weight_names + datasets:
-                 iterations, then Adam's m per trainable weight, v per trainable weight, then (1,)-shaped vhat stubs).
+                 the optimizer class' optimizer.weights: [iterations] + one array per trainable weight per state block, e.g.
+                 Adam: iterations, m, v, then vhat ((1,)-shaped stubs without amsgrad); SGD: iterations, m; RMSprop: a;
+                 engine.Optimizer._layout).
 `model.layers` order: Sequential = layers as added (no InputLayer); functional Model = Keras' depth order (Network
 ._init_graph_network): depth = longest distance to an output, ties by post-order index of a DFS from the outputs.
 A nested model is ONE layer whose weights are trainable_weights + non_trainable_weights (Keras' Layer.weights).
@@ -18,7 +20,7 @@ import json
 import numpy as np
 
 from . import h5lite
-from .engine import Adam, Input, Layer, Model, Sequential, to_snake_case  # noqa: F401
+from .engine import Adam, Input, Layer, Model, Sequential, optimizer_from_config, to_snake_case  # noqa: F401
 
 KERAS_VERSION = '2.2.4'
 BACKEND = 'tensorflow'
@@ -423,21 +425,20 @@ def save_model(model, path, include_optimizer=True, writer=None):
     opt = model.optimizer
     if include_optimizer and opt is not None:
         w.root.attrs['training_config'] = json.dumps({
-            'optimizer_config': {'class_name': 'Adam', 'config': {'lr': opt.lr, 'beta_1': opt.beta_1, 'beta_2': opt.beta_2, 'decay': 0.0,
-                                                                  'epsilon': opt.epsilon, 'amsgrad': False}},
+            'optimizer_config': {'class_name': type(opt).__name__, 'config': opt.get_config()},
             'loss': _loss_json(model.loss), 'metrics': list(model.metrics or []), 'sample_weight_mode': None, 'loss_weights': None}).encode('utf-8')
         if opt.state is not None and model._train_params:
+            # keras: optimizer.weights in model.trainable_weights order -- [iterations] (if the class saves it) + one block per state array;
+            # names in the scheme of a first compile, training/<Class>/Variable[_k]:0 (readers go by the weight_names order, never by name)
             og = w.root.create_group('optimizer_weights')
-            mv = opt.param_moments(model._keras_train_order())      # keras: model.trainable_weights order
-            names = ['Adam/iterations:0']
-            og.create_dataset(names[0], np.asarray(opt.iterations, np.int64))
-            k = 0
-            for arrs in ([m for m, _ in mv], [v for _, v in mv], [np.zeros((1,), np.float32) for _ in mv]):
-                for a in arrs:
-                    n = 'training/Adam/Variable%s:0' % ('' if k == 0 else '_%d' % k)
-                    og.create_dataset(n, np.asarray(a, np.float32))
-                    names.append(n)
-                    k += 1
+            cls = type(opt).__name__
+            vals = opt.get_keras_weights(model._keras_train_order())
+            names = []
+            if opt.SAVES_ITERATIONS:
+                names.append('%s/iterations:0' % cls)
+            names += ['training/%s/Variable%s:0' % (cls, '' if k == 0 else '_%d' % k) for k in range(len(vals) - len(names))]
+            for n, a in zip(names, vals):
+                og.create_dataset(n, a if n.endswith('iterations:0') else np.asarray(a, np.float32))
             og.attrs['weight_names'] = np.array([n.encode('utf-8') for n in names], dtype='S')
     save_private_state(w.root, model)
     _write(w, path, writer)
@@ -454,15 +455,32 @@ def load_model(path, custom_objects=None, compile=True):
     tc = f.attrs.get('training_config')
     if compile and tc is not None:
         tc = json.loads(tc.decode('utf-8') if isinstance(tc, bytes) else tc)
-        oc = tc['optimizer_config']
-        if oc['class_name'] != 'Adam':
-            raise NotImplementedError('optimizer %s' % oc['class_name'])
-        c = oc['config']
-        model.compile(loss=tc['loss'], optimizer=Adam(lr=c['lr'], beta_1=c['beta_1'], beta_2=c['beta_2'], epsilon=c.get('epsilon'), decay=c.get('decay', 0.0)),
-                      metrics=tc.get('metrics') or [])
+        # any of engine.OPTIMIZERS with its own config, clipnorm / clipvalue included.  RMSprop, Adagrad and Adadelta files carry no iteration
+        # count (Keras 2.2.4 does not save it): a resumed run restarts at iterations = 0, and with decay > 0 restarts the decay schedule
+        model.compile(loss=tc['loss'], optimizer=optimizer_from_config(tc['optimizer_config']), metrics=tc.get('metrics') or [])
         if 'optimizer_weights' in f:
             og = f['optimizer_weights']
             names = _decode_list(og.attrs.get('weight_names'))
             vals = [og[n].value for n in names]
             model._pending_optimizer_weights = vals      # applied when the optimizer state is bound (first device use)
     return model
+
+
+def load_optimizer_weights(model, path):
+    """The optimizer state (optimizer_weights) of the model file `path` into the compiled `model`, whose optimizer must be of the class the file
+    records: what keras.models.load_model restores, for a model that is rebuilt and compiled by the caller (scripts/bbh_train.py --old-model).
+    Applied at the first device step, or now if the optimizer state is already bound.  A file without optimizer_weights leaves the state alone."""
+    f = h5lite.File(path)
+    tc = f.attrs.get('training_config')
+    if tc is None or 'optimizer_weights' not in f:
+        return False
+    oc = json.loads(tc.decode('utf-8') if isinstance(tc, bytes) else tc)['optimizer_config']
+    if oc['class_name'] != type(model.optimizer).__name__:
+        raise ValueError('%s holds %s state; the model is compiled with %s' % (path, oc['class_name'], type(model.optimizer).__name__))
+    og = f['optimizer_weights']
+    vals = [og[n].value for n in _decode_list(og.attrs.get('weight_names'))]
+    if getattr(model, '_bound', False):
+        model.optimizer.set_keras_weights(model._keras_train_order(), vals)
+    else:
+        model._pending_optimizer_weights = vals
+    return True

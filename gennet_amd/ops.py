@@ -646,6 +646,34 @@ def adam_step(p, g, m, v, lr_t, b1, b2, eps):
         _lib.call('gn_adam_step', _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr_t), float(b1), float(b2), float(eps), _stream())
 
 
+OPT_RULES = {'sgd': 0, 'rmsprop': 1, 'adagrad': 2, 'adadelta': 3, 'adamax': 4, 'adam': 5, 'amsgrad': 6}
+
+
+def optim_step(rule, p, g, states, lr, h0=0.0, h1=0.0, eps=0.0, nesterov=False, clip_scale=None, clipvalue=0.0):
+    """One fused update of the Keras rule `rule` (OPT_RULES) over p with gradient g and the rule's state tensors (engine.Optimizer).
+    lr: a python float or a DevScalar (captured step); clip_scale: None or a (1,) fp32 device tensor (optim_clip_factor)."""
+    _chk(p, g, *states)
+    st = [_p(s) for s in states] + [None] * (3 - len(states))
+    dyn = isinstance(lr, DevScalar)
+    _lib.call('gn_optim_step', OPT_RULES[rule], _p(p), _p(g), st[0], st[1], st[2], p.numel(), 0.0 if dyn else float(lr), lr.ptr if dyn else None,
+              float(h0), float(h1), float(eps), 1 if nesterov else 0, None if clip_scale is None else _p(clip_scale), float(clipvalue), _stream())
+
+
+def optim_sumsq_slots(n):
+    return _lib.size('gn_optim_sumsq_slots', int(n))
+
+
+def optim_sumsq(g, partials):
+    """fp64 partial sums of g^2 into partials[:optim_sumsq_slots(g.numel())]."""
+    _chk(g)
+    _lib.call('gn_optim_sumsq', _p(g), g.numel(), _p(partials), _stream())
+
+
+def optim_clip_factor(partials, clipnorm, factor):
+    """factor[0] = clipnorm / norm if norm >= clipnorm else 1, norm = sqrt(sum of all partials) (fixed order)."""
+    _lib.call('gn_optim_clip_factor', _p(partials), partials.numel(), float(clipnorm), _p(factor), _stream())
+
+
 class DevScalar(object):
     """Address of one step-varying scalar in a step graph's parameter block (engine.StepGraph.slot)."""
 

@@ -269,6 +269,32 @@ int gn_mse_loss(const float* p, const float* y, float* dp, float* out, int B, in
  * m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (host). */
 int gn_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, void* stream);
 
+/* ---- Keras 2.2.4 optimizers beyond the default Adam pass --------------------------------------------------
+ * bbhMahoGANy.py:43 imports RMSprop, Adagrad, Adadelta, Adamax; the earlier GenNet versions train with SGD(lr=lr)
+ * (2_model_version/no_weight_code/noise_gan.py:75, subtract_model.py:211, ht_noise_subtract_version/nn.py:123), and the reference's
+ * g_model.hdf5 (tests/golden/keras_h5/) was compiled with SGD.  One fused pass per segment: p, g and the rule's state are read once,
+ * p and the state written once.  lr is this step's lr_eff = lr / (1 + decay * iterations) (SGD, RMSprop, Adagrad, Adadelta) or
+ * lr_t = lr_eff sqrt(1 - b2^t) / (1 - b1^t) (Adam) | lr_eff / (1 - b1^t) (Adamax), computed on the host; with lr_dev != NULL it is read
+ * from device memory instead (a captured step).  Before the rule, g <- g * (*clip_scale) when clip_scale != NULL, then
+ * g <- clip(g, -clipvalue, clipvalue) when clipvalue > 0.  State arrays (s0, s1, s2) by rule, NULL where unused:
+ *   GN_OPT_SGD      m              h0 = momentum (nesterov 0 | 1)
+ *   GN_OPT_RMSPROP  a              h0 = rho
+ *   GN_OPT_ADAGRAD  a
+ *   GN_OPT_ADADELTA a, d           h0 = rho
+ *   GN_OPT_ADAMAX   m, u           h0 = beta_1, h1 = beta_2
+ *   GN_OPT_ADAM     m, v           h0 = beta_1, h1 = beta_2
+ *   GN_OPT_AMSGRAD  m, v, vhat     h0 = beta_1, h1 = beta_2
+ * n == 0 is a no-op; any n and alignment (float4 body where the arrays are mutually 16-byte aligned). */
+enum gn_optim_rule { GN_OPT_SGD = 0, GN_OPT_RMSPROP = 1, GN_OPT_ADAGRAD = 2, GN_OPT_ADADELTA = 3, GN_OPT_ADAMAX = 4, GN_OPT_ADAM = 5, GN_OPT_AMSGRAD = 6 };
+int gn_optim_step(int rule, float* p, const float* g, float* s0, float* s1, float* s2, size_t n, float lr, const float* lr_dev, float h0, float h1,
+                  float eps, int nesterov, const float* clip_scale, float clipvalue, void* stream);
+/* Keras' clipnorm (optimizers.py get_gradients) over ALL trained weights of a compiled model, without host synchronisation or atomics:
+ * gn_optim_sumsq writes gn_optim_sumsq_slots(n) fp64 partial sums of g^2 of one segment to partials[0 ..); gn_optim_clip_factor adds
+ * `count` partials in a fixed order and writes *factor = clipnorm / norm if norm >= clipnorm, else 1 (fp32; norm = sqrt(sum) in fp32). */
+size_t gn_optim_sumsq_slots(size_t n);
+int gn_optim_sumsq(const float* g, size_t n, double* partials, void* stream);
+int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, void* stream);
+
 /* ---- hipGraph capture of a whole train step (bbhMahoGANy.py:1153-1168, :1241-1299 at the script's own batch size 8, where the loop is
  * launch-bound): every launch of the library is stream-ordered and allocation-free, so train_on_batch can be captured on the launch stream and
  * replayed.  Scalars that change from step to step would be frozen into the graph as by-value kernel arguments; these entry points read them

@@ -42,6 +42,12 @@ def main():
     ap.add_argument('--graph', action='store_true', help='replay the two loop bodies as captured hipGraphs (single GPU, n_noise_real 1): the same numbers bit for '
                                                        'bit, no per-iteration host synchronisation between the read-outs')
     ap.add_argument('--pe-cadence', type=int, default=1000, help='CNN progress read-out every so many iterations (:1176, :1200)')
+    ap.add_argument('--optimizer', default='adam', choices=('adam', 'sgd', 'rmsprop', 'adagrad', 'adadelta', 'adamax'),
+                    help="every network's optimizer: adam is the script's Adam(lr, beta_1=0.5) (:1101-1119), the others Keras' classes with Keras defaults "
+                         "apart from --lr")
+    ap.add_argument('--decay', type=float, default=0.0, help="Keras' decay: lr / (1 + decay * iterations)")
+    ap.add_argument('--clipnorm', type=float, default=0.0, help="Keras' clipnorm over all trained weights of each compiled model (0: off)")
+    ap.add_argument('--clipvalue', type=float, default=0.0, help="Keras' clipvalue, after clipnorm (0: off)")
     ap.add_argument('--old-model', action='store_true', help='do_old_model (:1133-1138): start all four networks from the files of an earlier run in --out')
     ap.add_argument('--only-old-pe-model', action='store_true', help='do_only_old_pe_model (:1141-1142): load best_models/signal_pe.h5 and skip the CNN loop')
     ap.add_argument('--sanity-check', default=None,
@@ -50,7 +56,7 @@ def main():
                     help='mc_q pickle of scripts/get_lalinf_pars.py: the overlap of the GAN posterior with it is scored at every cadence (:1345-1356)')
     args = ap.parse_args()
 
-    from gennet_amd import bbh, dist, engine, hostio, templates as T
+    from gennet_amd import bbh, dist, engine, hostio, keras_io, templates as T
     dp = dist.init()
     rank, world = (dp.rank, dp.world_size) if dp else (0, 1)
     engine.set_init_seed(1)
@@ -63,7 +69,8 @@ def main():
     with open('data/%s0%s.sav' % (args.event_name, args.tag), 'rb') as f:            # :1027-1028
         noise_signal = np.reshape(pickle.load(f, encoding='latin1') * args.event_scale, (args.n_pix, 1))
 
-    nets = bbh.build_and_compile(noise_signal, args.n_pix, lr=args.lr, data_parallel=dp, chi_loss=args.chi_loss, n_sig=args.n_sig)
+    opt = bbh.optimizer_factory(args.optimizer, args.lr, args.decay, args.clipnorm or None, args.clipvalue or None)
+    nets = bbh.build_and_compile(noise_signal, args.n_pix, lr=args.lr, data_parallel=dp, chi_loss=args.chi_loss, n_sig=args.n_sig, optimizer=opt)
     if dp:
         for m in (nets.generator, nets.signal_discriminator, nets.signal_pe):
             dp.sync_model(m)
@@ -82,6 +89,7 @@ def main():
             sanity = engine.to_device(np.asarray(pickle.load(f, encoding='latin1'), np.float32).reshape(-1, args.n_pix, 1))
     if args.old_model:                                                                # :1133-1138
         nets.signal_pe.load_weights(os.path.join(args.out, 'best_models/signal_pe.h5'))
+        keras_io.load_optimizer_weights(nets.signal_pe, os.path.join(args.out, 'best_models/signal_pe.h5'))   # the state model.save wrote with it
         nets.signal_discriminator.load_weights(os.path.join(args.out, 'discriminator.h5'))
         nets.signal_discriminator_on_generator.load_weights(os.path.join(args.out, 'signal_dis_on_gen.h5'))
         nets.generator.load_weights(os.path.join(args.out, 'generator.h5'))
