@@ -1,5 +1,6 @@
-// extern "C" surface of libgennet_hip.so (see include/gennet_hip.h).  Argument checking, tap-table construction and
-// kernel-family dispatch live here; no torch types, no allocation, no synchronisation.
+// extern "C" surface of libgennet_hip.so (see include/gennet_hip.h).  Argument checking, tap-table construction, the library switches and
+// the kernel-family selection of every convolution (select_conv / select_dgrad / select_wgrad: one table below) live here; no torch types, no
+// allocation, no synchronisation.
 #include <stdarg.h>
 #include <algorithm>
 #include <mutex>
@@ -68,79 +69,145 @@ void prof_end(hipStream_t s, double flop, int kind, double bytes) {
   g_prof.push_back({g_cur, b, flop, kind, bytes});
 }
 
-static void fwd_taps(ConvTaps* t, int k, int stride, int pad_left) {
-  t->ntaps = k;
-  t->in_stride = stride;
-  for (int j = 0; j < k; ++j) {
-    t->off[j] = j - pad_left;
-    t->widx[j] = j;
-  }
-  t->out_stride = 1;
-  t->out_off = 0;
+const Switches& switches() {
+  static const Switches sw = [] {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    const char* gflop = getenv("GN_BF16X3_MIN_GFLOP");
+    return Switches{on("GN_CONV_NOPIPE"),  on("GN_CONV_NODMA"),   on("GN_CONV_NOMERGE"),    on("GN_CONV_NONARROW"), on("GN_CONV_NOPATCH"),
+                    on("GN_WGRAD_NOPIPE"), on("GN_BF16X3_NO_MERGE"), gflop ? atof(gflop) : 50.0};
+  }();
+  return sw;
 }
 
-// Conv arithmetic (gn_set_conv_math): 0 = direct fp32 MFMA kernels only; 1 = opt-in bf16 x 3 operand split for the launches it supports and that
-// are large enough to gain from it; 2 = transform-domain fp32 (Cook-Toom F(2,5), conv_wino.hip) for every unit-stride 5-tap launch it supports --
-// decided by the layer's shape alone, never by the batch size, so a batch and its chunks take the same kernel and agree bit for bit.  Everything
-// else stays on the direct fp32 kernels.
+// ---- kernel-family selection ----------------------------------------------------------------------------------------------------------------
+// Conv arithmetic (gn_set_conv_math): 0 = direct fp32 MFMA kernels only; 1 = opt-in bf16 x 3 operand split; 2 = transform-domain fp32 (the
+// engine's default).  select_conv (forward, each phase of a data gradient, Dense data gradient), select_dgrad (the merged stride-2 data gradient)
+// and select_wgrad decide the family from the launch's shape, the conv math and the switches alone -- never from a workspace size -- so forward,
+// data gradient and weight gradient of a layer use the same arithmetic.  The launch code then checks that the workspace holds what the chosen
+// family needs (GN_EWORKSPACE with the size otherwise) and never re-selects.
+//
+//   family   directions (math)      shape rule, besides the kernel's own *_supported / *_kind           workspace (conv-math | caller's)
+//   small    fwd, dgrad, wgrad      Cin <= 4 or Cout <= 4                                               - | wgrad_small_workspace_bytes
+//   wino     fwd, wgrad (2)         5 taps, stride 1, Cin >= 32 (fwd); 6 Cin Cout floats <= 64 MiB      6 Cin Cout floats | wgrad_wino_workspace_bytes
+//   wino_s2  fwd, dgrad, wgrad (2)  5 taps, stride 2; 7 Cin Cout floats <= 64 MiB                       7 Cin Cout floats | wgrad_wino_s2_workspace_bytes
+//   bf16x3   fwd, dgrad, wgrad (1)  Cin, Cout >= 256 and GN_BF16X3_MIN_GFLOP (split_worth_it)          the split operands | wgrad_workspace_bytes
+//   merged   dgrad                  stride 2, 5 taps, few tiles; not bf16x3, NOMERGE, NOPIPE or NODMA   - | -
+//   direct   everything else        conv_mfma_dispatch / wgrad_mfma_dispatch pick tile and member       - | wgrad_workspace_bytes
 static int g_conv_math = 0;
 static void* g_conv_ws = nullptr;
 static size_t g_conv_ws_bytes = 0;
+constexpr size_t kWinoKernelBytes = 64ull << 20;      // largest transformed kernel of the transform-domain families = the workspace math 2 needs
 
-// The output phases of one strided data gradient read the same dy and the same kernel: under the opt-in split math the first phase splits them (ALL k
-// taps of the kernel, so that the planes' layout does not depend on the phase), the later phases reuse the planes (8 of the 28 split passes of a
-// BASELINE step are such repeats).  Set by dgrad_impl around its phase loop.
-static int g_phase_w_taps = 0;
-static bool g_phase_have_split = false;
-struct PhaseScope {
-  explicit PhaseScope(int w_taps) { g_phase_w_taps = w_taps; g_phase_have_split = false; }
-  ~PhaseScope() { g_phase_w_taps = 0; g_phase_have_split = false; }
-};
-
-// Size gate of the opt-in split: below ~50 GFLOP a launch does not keep the 256-row blocks of the split kernels busy for more than a round or two and
-// the split pass in front of it is pure latency (at the reference script's own batch 8 every launch is below it: the opt-in then changes nothing there
-// instead of costing 1 %).  GN_BF16X3_MIN_GFLOP: A/B switch.
+// Size gate of the opt-in split, the one predicate for all its launches.  The split pass costs ~10 bytes per input element per launch, the conv
+// gains ~0.02 ps per element and output channel, so small-Cout layers gain little and small-Cin layers (few K chunks) lose to the prologue; below
+// ~50 GFLOP a launch does not keep the 256-row blocks of the split kernels busy for more than a round or two and the split pass in front of it is
+// pure latency (at the reference script's own batch 8 every launch is below it: the opt-in then changes nothing there instead of costing 1 %).
 static bool split_worth_it(int B, int M, int ntaps, int Cin, int Cout) {
-  static const double min_gflop = getenv("GN_BF16X3_MIN_GFLOP") ? atof(getenv("GN_BF16X3_MIN_GFLOP")) : 50.0;
-  return 2.0 * B * (double)M * ntaps * Cin * Cout >= min_gflop * 1e9;
+  constexpr int min_cin = 256, min_cout = 256;
+  return Cin >= min_cin && Cout >= min_cout && 2.0 * B * (double)M * ntaps * Cin * Cout >= switches().bf16x3_min_gflop * 1e9;
+}
+// ... of a forward / data-gradient launch; w_taps > 0: a phase (or both) of a w_taps-tap layer's strided data gradient, decided on the whole layer
+static bool split_worth_it(const ConvArgs& a, int w_taps) {
+  return w_taps > 0 ? split_worth_it(a.B, (a.Ly + 1) / 2, w_taps, a.Cin, a.Cout) : split_worth_it(a.B, a.M, a.t.ntaps, a.Cin, a.Cout);
 }
 
-static int conv_dispatch(const ConvArgs& a, hipStream_t s) {
-  if (a.Cin <= 4) return conv_smallcin_dispatch(a, s);
-  if (a.Cout <= 4) return conv_smallcout_dispatch(a, s);
-  if (g_conv_math == 2 && a.Cin >= 32 && conv_wino_supported(a) && conv_wino_workspace_bytes(a.Cin, a.Cout) <= g_conv_ws_bytes)
-    return conv_wino_run(a, g_conv_ws, g_conv_ws_bytes, s);
-  if (g_conv_math == 2 && conv_wino_s2_kind(a) == 1 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= g_conv_ws_bytes)
-    return conv_wino_s2_run(a, g_conv_ws, g_conv_ws_bytes, s);                 // stride-2 forward: F(2,3) + F(2,2)
-  // size threshold of the opt-in split: the split pass costs ~10 bytes per input element per launch, the conv gains ~0.02 ps per element and output
-  // channel, so small-Cout layers gain little and small-Cin layers (few K chunks) lose to the prologue
-  constexpr int min_cin = 256, min_cout = 256;
-  if (g_conv_math == 1 && a.Cin >= min_cin && a.Cout >= min_cout && conv_bf16x3_supported(a) &&
-      (g_phase_w_taps > 0 ? split_worth_it(a.B, (a.Ly + 1) / 2, g_phase_w_taps, a.Cin, a.Cout) :      // (every phase of one data gradient decides alike)
-                            split_worth_it(a.B, a.M, a.t.ntaps, a.Cin, a.Cout))) {
-    int w_taps = 0;
-    for (int j = 0; j < a.t.ntaps; ++j) w_taps = std::max(w_taps, a.t.widx[j] + 1);
-    const bool phased = g_phase_w_taps > 0;
-    if (phased) w_taps = g_phase_w_taps;
-    // which kernel a launch takes depends on its shape alone: a workspace too small for it is an error, not a silent change of arithmetic
-    if (conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, w_taps) > g_conv_ws_bytes) {
-      set_error("conv (bf16x3 math): the split operands of this launch need %zu bytes, the workspace has %zu -- raise GENNET_CONV_WS_GB / ops.set_conv_math(workspace_gb=)",
-                conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, w_taps), g_conv_ws_bytes);
-      return GN_EWORKSPACE;
-    }
-    if (!(phased && g_phase_have_split)) {
-      int rc = conv_bf16x3_split(a, w_taps, g_conv_ws, g_conv_ws_bytes, true, true, s);
-      if (rc) return rc;
-      g_phase_have_split = phased;
-    }
-    return conv_bf16x3_run(a, w_taps, g_conv_ws, s);
+enum ConvFamily { CONV_SMALL, CONV_WINO, CONV_WINO_S2, CONV_BF16X3, CONV_DIRECT };
+
+// forward, one data-gradient phase, Dense data gradient
+static ConvFamily select_conv(const ConvArgs& a, int w_taps) {
+  if (a.Cin <= 4 || a.Cout <= 4) return CONV_SMALL;
+  if (g_conv_math == 2 && a.Cin >= 32 && conv_wino_supported(a) && conv_wino_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return CONV_WINO;
+  if (g_conv_math == 2 && conv_wino_s2_kind(a) == 1 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return CONV_WINO_S2;      // stride-2 forward: F(2,3) + F(2,2)
+  if (g_conv_math == 1 && split_worth_it(a, w_taps) && conv_bf16x3_supported(a)) return CONV_BF16X3;
+  return CONV_DIRECT;
+}
+
+enum DgradFamily { DGRAD_WINO_S2, DGRAD_BF16X3_MERGED, DGRAD_MERGED, DGRAD_PHASES };
+
+// the data gradient of a stride-2, 5-tap layer; a = its merged two-phase form (dgrad_impl).  DGRAD_PHASES: one select_conv launch per phase
+static DgradFamily select_dgrad(const ConvArgs& a) {
+  if (a.Ly < 2 || a.Cin <= 4 || a.Cout <= 4) return DGRAD_PHASES;
+  if (g_conv_math == 2 && conv_wino_s2_kind(a) == 2 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return DGRAD_WINO_S2;      // both phases, F(2,3) and F(2,2)
+  const Switches& sw = switches();
+  const bool split = g_conv_math == 1 && split_worth_it(a, 5);
+  if (split) return !sw.bf16x3_no_merge && conv_bf16x3_merged_kind(a) ? DGRAD_BF16X3_MERGED : DGRAD_PHASES;
+  // the merged member of the pipelined LDS-DMA family: every switch that takes that family out takes it out too
+  if (!sw.conv_nomerge && !sw.conv_nopipe && !sw.conv_nodma && conv_pipe_merged_supported(a)) return DGRAD_MERGED;
+  return DGRAD_PHASES;
+}
+
+enum WgradFamily { WGRAD_SMALL, WGRAD_WINO, WGRAD_WINO_S2, WGRAD_BF16X3, WGRAD_DIRECT };
+
+static WgradFamily select_wgrad(const WgradArgs& a) {
+  if (a.Cin <= 4 || a.Cout <= 4) return WGRAD_SMALL;
+  if (g_conv_math == 2 && wgrad_wino_supported(a) && conv_wino_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return WGRAD_WINO;
+  if (g_conv_math == 2 && wgrad_wino_s2_supported(a) && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return WGRAD_WINO_S2;
+  if (g_conv_math == 1 && split_worth_it(a.B, a.M, a.ntaps, a.Cin, a.Cout) && wgrad_bf16x3_supported(a)) return WGRAD_BF16X3;
+  return WGRAD_DIRECT;
+}
+
+// what the weight-gradient family needs of the CALLER's workspace (the bias-gradient pass needs bias_grad_ws on top, not beside)
+static size_t wgrad_ws_need(WgradFamily f, const WgradArgs& a) {
+  switch (f) {
+    case WGRAD_SMALL: return wgrad_small_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);
+    case WGRAD_WINO: return wgrad_wino_workspace_bytes(a.B, a.M, a.Cin, a.Cout);          // six point slabs per split
+    case WGRAD_WINO_S2: return wgrad_wino_s2_workspace_bytes(a.B, a.M, a.Cin, a.Cout);    // seven
+    default: return wgrad_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);              // direct and bf16x3: the same partial slabs
   }
-  return conv_mfma_dispatch(a, s);
+}
+
+static int ws_check(const char* what, size_t need, size_t have) {      // what = "conv-math" (GENNET_CONV_WS_GB, ops.set_conv_math) or the entry point
+  if (need <= have) return GN_OK;
+  set_error("%s workspace: the selected kernel needs %zu bytes, the workspace has %zu", what, need, have);
+  return GN_EWORKSPACE;
+}
+
+// The phases of one strided data gradient read the same dy and kernel: under the opt-in split the first phase splits them (ALL w_taps taps, so the
+// planes' layout does not depend on the phase), the later ones reuse the planes (8 of the 28 split passes of a BASELINE step are such repeats).
+struct Phases { int w_taps; bool have_split; };
+
+// one forward / data-gradient-phase launch on the family select_conv picks; ph: the phase state of a strided data gradient, else NULL
+static int conv_run(const ConvArgs& a, hipStream_t s, Phases* ph = nullptr) {
+  const ConvFamily f = select_conv(a, ph ? ph->w_taps : 0);
+  int w_taps = ph ? ph->w_taps : 0;                      // taps of the kernel the split covers
+  for (int j = 0; !ph && j < a.t.ntaps; ++j) w_taps = std::max(w_taps, a.t.widx[j] + 1);
+  const size_t need = f == CONV_WINO ? conv_wino_workspace_bytes(a.Cin, a.Cout) : f == CONV_WINO_S2 ? conv_wino_s2_workspace_bytes(a.Cin, a.Cout)
+                      : f == CONV_BF16X3 ? conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, w_taps) : 0;
+  if (int rc = ws_check("conv-math", need, g_conv_ws_bytes)) return rc;
+  switch (f) {
+    case CONV_SMALL: return a.Cin <= 4 ? conv_smallcin_dispatch(a, s) : conv_smallcout_dispatch(a, s);
+    case CONV_WINO: return conv_wino_run(a, g_conv_ws, g_conv_ws_bytes, s);
+    case CONV_WINO_S2: return conv_wino_s2_run(a, g_conv_ws, g_conv_ws_bytes, s);
+    case CONV_BF16X3:
+      if (!(ph && ph->have_split)) {
+        int rc = conv_bf16x3_split(a, w_taps, g_conv_ws, g_conv_ws_bytes, true, true, s);
+        if (rc) return rc;
+        if (ph) ph->have_split = true;
+      }
+      return conv_bf16x3_run(a, w_taps, g_conv_ws, s);
+    default: return conv_mfma_dispatch(a, s);
+  }
+}
+
+// ConvArgs of a forward launch (Dense: B = 1, L = Lout = the batch, k = 1)
+static ConvArgs fwd_args(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k, int stride, int pad_left,
+                         int Lout, int act, float act_param) {
+  ConvArgs a = {};
+  a.x = x; a.w = w; a.bias = bias; a.y = y;
+  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
+  a.t.ntaps = k; a.t.in_stride = stride; a.t.out_stride = 1;
+  for (int j = 0; j < k; ++j) { a.t.off[j] = j - pad_left; a.t.widx[j] = j; }
+  a.act = act; a.act_param = act_param;
+  return a;
 }
 
 static int set_conv_math_impl(int mode, void* workspace, size_t workspace_bytes) {
   GN_REQUIRE(mode >= 0 && mode <= 2, "set_conv_math: mode %d (0 = direct fp32, 1 = bf16x3, 2 = transform-domain fp32)", mode);
   GN_REQUIRE(mode == 0 || workspace, "set_conv_math: modes 1 and 2 need a device workspace");
+  if (mode == 2 && workspace_bytes < kWinoKernelBytes) {
+    set_error("set_conv_math: the transform-domain math needs a workspace of %zu bytes, got %zu", kWinoKernelBytes, workspace_bytes);
+    return GN_EWORKSPACE;
+  }
   g_conv_math = mode;
   g_conv_ws = mode ? workspace : nullptr;
   g_conv_ws_bytes = mode ? workspace_bytes : 0;
@@ -238,12 +305,8 @@ int gn_conv1d_fwd(const float* x, const float* w, const float* bias, float* y, i
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0, "conv1d_fwd: bad shape");
   GN_REQUIRE(pad_left >= 0 && stride * (Lout - 1) + k - pad_left <= L + k, "conv1d_fwd: Lout %d inconsistent with L %d k %d stride %d", Lout, L, k, stride);
   if (B == 0) return GN_OK;
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
-  fwd_taps(&a.t, k, stride, pad_left);
-  a.act = act; a.act_param = act_param;
-  return conv_dispatch(a, (hipStream_t)stream);
+  ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
+  return conv_run(a, (hipStream_t)stream);
 }
 
 int gn_set_conv_math(int mode, void* workspace, size_t workspace_bytes) { return set_conv_math_impl(mode, workspace, workspace_bytes); }
@@ -265,14 +328,10 @@ int gn_conv1d_fwd_stats(const float* x, const float* w, const float* bias, float
   GN_REQUIRE(B > 0 && L > 0 && Cin > 0 && Cout > 0 && Cout % 4 == 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0, "conv1d_fwd_stats: bad shape");
   GN_REQUIRE(pad_left >= 0 && stride * (Lout - 1) + k - pad_left <= L + k, "conv1d_fwd_stats: Lout %d inconsistent with L %d k %d stride %d", Lout, L, k, stride);
   GN_REQUIRE(ws_bytes >= gn_conv1d_fwd_stats_workspace(B, Lout, Cout), "conv1d_fwd_stats: workspace too small");
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
-  fwd_taps(&a.t, k, stride, pad_left);
-  a.act = GN_ACT_LINEAR; a.act_param = 0.f;
+  ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, GN_ACT_LINEAR, 0.f);
   int done = 0;
   a.stat_part = (double*)ws; a.stat_sums = sums; a.stat_done = &done;
-  int rc = conv_dispatch(a, s);
+  int rc = conv_run(a, s);
   if (rc || done) return rc;
   ColRedArgs r = {};                                     // the launched kernel had no statistics epilogue: one separate pass over y
   r.a = y; r.rows = (size_t)B * Lout; r.C = Cout;
@@ -284,11 +343,7 @@ int gn_conv1d_fwd_bf16x3(const float* x, const float* w, const float* bias, floa
   GN_REQUIRE(x && w && y && ws, "conv1d_fwd_bf16x3: null pointer");
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 5 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_fwd_bf16x3: bad shape");
   if (B == 0) return GN_OK;
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
-  fwd_taps(&a.t, k, stride, pad_left);
-  a.act = act; a.act_param = act_param;
+  ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
   GN_REQUIRE(conv_bf16x3_supported(a), "conv1d_fwd_bf16x3: needs Cin %% 16 == 0, Cout %% 64 == 0, k <= 5, stride 1");
   if (resplit) {
     int rc = conv_bf16x3_split(a, k, ws, ws_bytes, true, true, (hipStream_t)stream);
@@ -304,11 +359,7 @@ int gn_conv1d_fwd_wino(const float* x, const float* w, const float* bias, float*
   GN_REQUIRE(x && w && y && ws, "conv1d_fwd_wino: null pointer");
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k == 5 && stride == 1 && Lout > 0 && pad_left >= 0, "conv1d_fwd_wino: 5 taps, unit stride");
   if (B == 0) return GN_OK;
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
-  fwd_taps(&a.t, k, stride, pad_left);
-  a.act = act; a.act_param = act_param;
+  ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
   return conv_wino_run(a, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -318,13 +369,9 @@ int gn_conv1d_fwd_dropout(const float* x, const float* w, const float* bias, con
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 4 && Cout % 4 == 0 && k >= 1 && k <= 5 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_fwd_dropout: bad shape");
   GN_REQUIRE(rate >= 0.f && rate < 1.f, "conv1d_fwd_dropout: bad rate %f", rate);
   if (B == 0) return GN_OK;
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.Ly = Lout;
-  fwd_taps(&a.t, k, stride, pad_left);
-  a.act = act; a.act_param = act_param;
+  ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
   a.mask = mask; a.keep_scale = 1.0f / (1.0f - rate);
-  return conv_dispatch(a, (hipStream_t)stream);
+  return conv_run(a, (hipStream_t)stream);
 }
 
 int gn_conv1d_transpose_w(const float* w, float* wt, int k, int Cin, int Cout, void* stream) {
@@ -333,7 +380,54 @@ int gn_conv1d_transpose_w(const float* w, float* wt, int k, int Cin, int Cout, v
 }
 
 static int dgrad_impl(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, const float* gy,
-                      const uint8_t* gmask, int gact, float gparam, float grate, void* stream);
+                      const uint8_t* gmask, int gact, float gparam, float grate, void* stream) {
+  GN_REQUIRE(dy && wt && dx, "conv1d_dgrad: null pointer");
+  GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_dgrad: bad shape");
+  if (B == 0) return GN_OK;
+  // dx[b, tau, ci] = sum_{k', co} dy[b, t, co] * wt[k', co, ci]  with  stride*t + k' - pad_left == tau.
+  // Output phase p = tau mod stride uses the taps with (p + pad_left - k') divisible by stride, at dy row m + (p+pad_left-k')/stride.
+  // p < 0: both output phases of a stride-2, 5-tap layer in one launch, the taps in kernel order (tap kk belongs to phase (kk + pad_left) & 1)
+  auto phase_args = [&](int p) {
+    ConvArgs a = {};
+    a.x = dy; a.w = wt; a.bias = nullptr; a.y = dx;
+    a.B = B; a.Lin = Lout; a.Cin = Cout; a.Cout = Cin; a.Ly = L;
+    a.t.in_stride = 1; a.t.out_stride = stride;
+    a.act = GN_ACT_LINEAR;
+    a.gy = gy; a.gmask = gmask; a.gact = gact; a.gparam = gparam; a.gscale = 1.0f / (1.0f - grate);
+    a.M = (L - std::max(p, 0) + stride - 1) / stride;
+    a.t.out_off = p < 0 ? pad_left & 1 : p;                  // merged: the phase of the even taps (kk = 0, 2, 4); the odd ones write out_off_odd
+    if (p < 0) a.t.out_off_odd = 1 - (pad_left & 1);
+    for (int kk = 0; kk < k; ++kk) {
+      const int d = (p < 0 ? (kk + pad_left) & 1 : p) + pad_left - kk;
+      if (((d % stride) + stride) % stride) continue;
+      a.t.off[a.t.ntaps] = (d >= 0) ? d / stride : -((-d) / stride);
+      a.t.widx[a.t.ntaps++] = kk;
+    }
+    return a;
+  };
+  hipStream_t s = (hipStream_t)stream;
+  if (stride == 2 && k == 5) {
+    const ConvArgs a = phase_args(-1);
+    const DgradFamily f = select_dgrad(a);
+    const size_t need = f == DGRAD_WINO_S2 ? conv_wino_s2_workspace_bytes(a.Cin, a.Cout)
+                        : f == DGRAD_BF16X3_MERGED ? conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, 5) : 0;
+    if (int rc = ws_check("conv-math", need, g_conv_ws_bytes)) return rc;
+    if (f == DGRAD_WINO_S2) return conv_wino_s2_run(a, g_conv_ws, g_conv_ws_bytes, s);
+    if (f == DGRAD_MERGED) return conv_pipe_run_merged(a, s);
+    if (f == DGRAD_BF16X3_MERGED) {
+      int rc = conv_bf16x3_split(a, 5, g_conv_ws, g_conv_ws_bytes, true, true, s);
+      return rc ? rc : conv_bf16x3_run_merged(a, g_conv_ws, s);
+    }
+  }
+  Phases ph = {stride > 1 ? k : 0, false};
+  for (int p = 0; p < stride && p < L; ++p) {
+    const ConvArgs a = phase_args(p);
+    GN_REQUIRE(a.t.ntaps > 0, "conv1d_dgrad: phase %d has no taps (k %d < stride %d)", p, k, stride);
+    int rc = conv_run(a, s, stride > 1 ? &ph : nullptr);
+    if (rc) return rc;
+  }
+  return GN_OK;
+}
 
 int gn_conv1d_dgrad(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream) {
   return dgrad_impl(dy, wt, dx, B, L, Cin, Cout, k, stride, pad_left, Lout, nullptr, nullptr, GN_ACT_LINEAR, 0.f, 0.f, stream);
@@ -347,86 +441,17 @@ int gn_conv1d_dgrad_fused(const float* dy, const float* wt, float* dx, int B, in
   return dgrad_impl(dy, wt, dx, B, L, Cin, Cout, k, stride, pad_left, Lout, y_prev, mask_prev, act_prev, act_param_prev, mask_prev ? rate_prev : 0.f, stream);
 }
 
-static int dgrad_impl(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, const float* gy,
-                      const uint8_t* gmask, int gact, float gparam, float grate, void* stream) {
-  GN_REQUIRE(dy && wt && dx, "conv1d_dgrad: null pointer");
-  GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_dgrad: bad shape");
-  if (B == 0) return GN_OK;
-  // dx[b, tau, ci] = sum_{k', co} dy[b, t, co] * wt[k', co, ci]  with  stride*t + k' - pad_left == tau.
-  // Output phase p = tau mod stride uses the taps with (p + pad_left - k') divisible by stride, at dy row m + (p+pad_left-k')/stride.
-  if (stride == 2 && k == 5 && L >= 2 && Cin > 4 && Cout > 4) {
-    // both output phases in one launch where the pipelined kernel takes it (conv_pipe_try_merged): tap kk belongs to phase (kk + pad_left) & 1
-    ConvArgs a = {};
-    a.x = dy; a.w = wt; a.bias = nullptr; a.y = dx;
-    a.B = B; a.Lin = Lout; a.Cin = Cout; a.Cout = Cin;
-    a.M = (L + 1) / 2; a.Ly = L;
-    a.t.in_stride = 1; a.t.out_stride = 2; a.t.ntaps = 5;
-    for (int kk = 0; kk < 5; ++kk) {
-      const int p = (kk + pad_left) & 1;
-      const int d = p + pad_left - kk;                       // even by construction
-      a.t.off[kk] = (d >= 0) ? d / 2 : -((-d) / 2);
-      a.t.widx[kk] = kk;
-    }
-    a.t.out_off = pad_left & 1;                              // phase of the even taps (kk = 0, 2, 4)
-    a.t.out_off_odd = 1 - (pad_left & 1);
-    a.act = GN_ACT_LINEAR;
-    a.gy = gy; a.gmask = gmask; a.gact = gact; a.gparam = gparam; a.gscale = 1.0f / (1.0f - grate);
-    if (g_conv_math == 2 && conv_wino_s2_kind(a) == 2 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= g_conv_ws_bytes)
-      return conv_wino_s2_run(a, g_conv_ws, g_conv_ws_bytes, (hipStream_t)stream);      // both phases in the transform domain: F(2,3) and F(2,2) over the same dy rows
-    // opt-in split math: one launch for both phases where the 256-row blocks fill (the x fragments of tap pairs that read the same rows are read once)
-    constexpr int min_cin = 256, min_cout = 256;
-    static const bool no_merge = getenv("GN_BF16X3_NO_MERGE") != nullptr;            // A/B switch: the two phase launches (tests/test_bf16x3_gpu.py)
-    const bool split_ok = g_conv_math == 1 && a.Cin >= min_cin && a.Cout >= min_cout && split_worth_it(a.B, a.M, 5, a.Cin, a.Cout);
-    if (split_ok && !no_merge && conv_bf16x3_merged_kind(a)) {
-      if (conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, 5) > g_conv_ws_bytes) {
-        set_error("conv data gradient (bf16x3 math): the split operands need %zu bytes, the workspace has %zu", conv_bf16x3_workspace_bytes(a.B, a.Lin, a.Cin, a.Cout, 5),
-                  g_conv_ws_bytes);
-        return GN_EWORKSPACE;
-      }
-      int rc = conv_bf16x3_split(a, 5, g_conv_ws, g_conv_ws_bytes, true, true, (hipStream_t)stream);
-      if (rc) return rc;
-      return conv_bf16x3_run_merged(a, g_conv_ws, (hipStream_t)stream);
-    }
-    if (!split_ok) {
-      // the exact kernel's merged form (it takes the small launches): a launch the split leaves alone must find it exactly as on the default path
-      bool launched = false;
-      int rc = conv_pipe_try_merged(a, (hipStream_t)stream, &launched);
-      if (rc || launched) return rc;
-    }
-  }
-  PhaseScope phases(stride > 1 ? k : 0);
-  for (int p = 0; p < stride; ++p) {
-    if (p >= L) break;
-    ConvArgs a = {};
-    a.x = dy; a.w = wt; a.bias = nullptr; a.y = dx;
-    a.B = B; a.Lin = Lout; a.Cin = Cout; a.Cout = Cin;
-    a.M = (L - p + stride - 1) / stride; a.Ly = L;
-    a.t.in_stride = 1; a.t.out_stride = stride; a.t.out_off = p;
-    int nt = 0;
-    for (int kk = 0; kk < k; ++kk) {
-      const int d = p + pad_left - kk;
-      if (((d % stride) + stride) % stride) continue;
-      a.t.off[nt] = (d >= 0) ? d / stride : -((-d) / stride);
-      a.t.widx[nt] = kk;
-      ++nt;
-    }
-    GN_REQUIRE(nt > 0, "conv1d_dgrad: phase %d has no taps (k %d < stride %d)", p, k, stride);
-    a.t.ntaps = nt;
-    a.act = GN_ACT_LINEAR;
-    a.gy = gy; a.gmask = gmask; a.gact = gact; a.gparam = gparam; a.gscale = 1.0f / (1.0f - grate);
-    int rc = conv_dispatch(a, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return GN_OK;
+static WgradArgs wgrad_args(const float* x, const float* dy, void* ws, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout) {
+  WgradArgs a = {};
+  a.x = x; a.dy = dy; a.part = (float*)ws;
+  a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.ntaps = k; a.in_stride = stride;
+  for (int j = 0; j < k && j < 8; ++j) a.off[j] = j - pad_left;
+  return a;
 }
 
 size_t gn_conv1d_wgrad_workspace(int B, int L, int Cin, int Cout, int k, int stride, int Lout) {
-  (void)L;
-  size_t w = (Cin <= 4 || Cout <= 4) ? wgrad_small_workspace_bytes(B, Lout, Cin, Cout, k) : wgrad_workspace_bytes(B, Lout, Cin, Cout, k);
-  if (k == 5 && stride == 1 && Cin % 64 == 0 && Cout % 64 == 0) w = std::max(w, wgrad_wino_workspace_bytes(B, Lout, Cin, Cout));      // six point slabs per split
-  if (k == 5 && stride == 2 && Cin % 64 == 0 && Cout % 64 == 0) w = std::max(w, wgrad_wino_s2_workspace_bytes(B, Lout, Cin, Cout));   // seven
-  size_t b = bias_grad_ws((size_t)B * Lout, Cout);
-  return (w > b ? w : b) + 256;
+  const WgradArgs a = wgrad_args(nullptr, nullptr, nullptr, B, L, Cin, Cout, k, stride, 0, Lout);      // (the need does not depend on pad_left)
+  return std::max(wgrad_ws_need(select_wgrad(a), a), bias_grad_ws((size_t)B * Lout, Cout)) + 256;
 }
 
 int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes, int B, int L, int Cin, int Cout, int k, int stride,
@@ -434,40 +459,30 @@ int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void*
   GN_REQUIRE(x && dy && dw && ws, "conv1d_wgrad: null pointer");
   GN_REQUIRE(B > 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 5 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_wgrad: bad shape");
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (Cin <= 4 || Cout <= 4) {
-    WgradSmallArgs a = {};
-    a.x = x; a.dy = dy; a.part = (float*)ws;
-    a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.ntaps = k; a.in_stride = stride;
-    for (int j = 0; j < k; ++j) a.off[j] = j - pad_left;
-    rc = wgrad_small_dispatch(a, dw, ws_bytes, s);
-  } else {
-    WgradArgs a = {};
-    a.x = x; a.dy = dy; a.part = (float*)ws;
-    a.B = B; a.Lin = L; a.Cin = Cin; a.Cout = Cout; a.M = Lout; a.ntaps = k; a.in_stride = stride;
-    for (int j = 0; j < k; ++j) a.off[j] = j - pad_left;
-    a.db = db;
-    if (g_conv_math == 2 && wgrad_wino_supported(a) && ws_bytes >= wgrad_wino_workspace_bytes(B, Lout, Cin, Cout)) {
-      rc = wgrad_wino_run(a, dw, ws_bytes, s);                 // transform-domain weight gradient; the bias gradient takes the separate pass below
-      if (rc) return rc;
-      return db ? bias_grad(dy, db, (size_t)B * Lout, Cout, ws, ws_bytes, s) : GN_OK;
+  WgradArgs a = wgrad_args(x, dy, ws, B, L, Cin, Cout, k, stride, pad_left, Lout);
+  a.db = db;
+  const WgradFamily f = select_wgrad(a);
+  int rc = ws_check("conv1d_wgrad", wgrad_ws_need(f, a), ws_bytes);
+  if (rc) return rc;
+  switch (f) {
+    case WGRAD_SMALL: {
+      WgradSmallArgs sa = {x, dy, (float*)ws, B, L, Cin, Cout, Lout, k, stride};
+      std::copy(a.off, a.off + k, sa.off);
+      rc = wgrad_small_dispatch(sa, dw, ws_bytes, s);
+      break;
     }
-    if (g_conv_math == 2 && wgrad_wino_s2_supported(a) && ws_bytes >= wgrad_wino_s2_workspace_bytes(B, Lout, Cin, Cout)) {
-      rc = wgrad_wino_s2_run(a, dw, ws_bytes, s);              // ... of a stride-2 layer
-      if (rc) return rc;
-      return db ? bias_grad(dy, db, (size_t)B * Lout, Cout, ws, ws_bytes, s) : GN_OK;
-    }
-    constexpr int min_cin = 256, min_cout = 256;
-    if (g_conv_math == 1 && Cin >= min_cin && Cout >= min_cout && split_worth_it(B, Lout, k, Cin, Cout)) {
-      a.split_ws = g_conv_ws;
-      a.split_ws_bytes = g_conv_ws_bytes;
-    }
-    rc = wgrad_mfma_dispatch(a, dw, ws_bytes, s);
-    if (!rc && a.db_done) return GN_OK;                  // the weight-gradient kernel summed the bias gradient on the way
+    case WGRAD_WINO: rc = wgrad_wino_run(a, dw, s); break;           // transform domain; the bias gradient takes the separate pass below
+    case WGRAD_WINO_S2: rc = wgrad_wino_s2_run(a, dw, s); break;
+    case WGRAD_BF16X3:
+      rc = ws_check("conv-math", wgrad_bf16x3_workspace_bytes(B, Lout, Cin, Cout, stride), g_conv_ws_bytes);
+      if (!rc) rc = wgrad_bf16x3_dispatch(a, dw, g_conv_ws, g_conv_ws_bytes, s);
+      break;
+    default:
+      rc = wgrad_mfma_dispatch(a, dw, ws_bytes, s);
+      if (!rc && a.db_done) return GN_OK;                  // the weight-gradient kernel summed the bias gradient on the way
   }
   if (rc) return rc;
-  if (db) rc = bias_grad(dy, db, (size_t)B * Lout, Cout, ws, ws_bytes, s);
-  return rc;
+  return db ? bias_grad(dy, db, (size_t)B * Lout, Cout, ws, ws_bytes, s) : GN_OK;
 }
 
 int gn_conv2d_w2_fold(const float* w, const float* bias, float* wf, float* biasf, int kh, int Cin, int Cout, void* stream) {
@@ -492,12 +507,7 @@ int gn_dense_fwd(const float* x, const float* w, const float* bias, float* y, in
   GN_REQUIRE(x && w && y && B >= 0 && in > 0 && out > 0, "dense_fwd: bad arguments");
   if (B == 0) return GN_OK;
   if (out <= 4) return dense_small_fwd(x, w, bias, y, B, in, out, act, act_param, (hipStream_t)stream);
-  ConvArgs a = {};
-  a.x = x; a.w = w; a.bias = bias; a.y = y;
-  a.B = 1; a.Lin = B; a.Cin = in; a.Cout = out; a.M = B; a.Ly = B;
-  fwd_taps(&a.t, 1, 1, 0);
-  a.act = act; a.act_param = act_param;
-  return conv_mfma_dispatch(a, (hipStream_t)stream);
+  return conv_mfma_dispatch(fwd_args(x, w, bias, y, 1, B, in, out, 1, 1, 0, B, act, act_param), (hipStream_t)stream);
 }
 
 size_t gn_dense_bwd_workspace(int B, int in, int out) {
@@ -527,17 +537,10 @@ int gn_dense_bwd(const float* x, const float* w, const float* dy, float* dx, flo
   if (dx) {
     rc = transpose_w(w, wt, 1, in, out, s);
     if (rc) return rc;
-    ConvArgs a = {};
-    a.x = dy; a.w = wt; a.y = dx;
-    a.B = 1; a.Lin = B; a.Cin = out; a.Cout = in; a.M = B; a.Ly = B;
-    fwd_taps(&a.t, 1, 1, 0);
-    a.act = GN_ACT_LINEAR;
-    rc = conv_dispatch(a, s);
+    rc = conv_run(fwd_args(dy, wt, nullptr, dx, 1, B, out, in, 1, 1, 0, B, GN_ACT_LINEAR, 0.f), s);
     if (rc) return rc;
   }
-  WgradArgs g = {};
-  g.x = x; g.dy = dy; g.part = (float*)ws2;
-  g.B = 1; g.Lin = B; g.Cin = in; g.Cout = out; g.M = B; g.ntaps = 1; g.in_stride = 1; g.off[0] = 0;
+  WgradArgs g = wgrad_args(x, dy, ws2, 1, B, in, out, 1, 1, 0, B);
   rc = wgrad_mfma_dispatch(g, dw, ws2_bytes, s);
   if (rc) return rc;
   if (db) rc = bias_grad(dy, db, (size_t)B, out, ws2, ws2_bytes, s);

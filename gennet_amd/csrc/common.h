@@ -22,6 +22,14 @@ namespace gn {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
+// A/B switches of the library, read from the environment once per process by switches() (capi.hip) and nowhere else
+struct Switches {
+  bool conv_nopipe, conv_nodma, conv_nomerge, conv_nonarrow, conv_nopatch;   // GN_CONV_NOPIPE, _NODMA, _NOMERGE, _NONARROW, _NOPATCH
+  bool wgrad_nopipe, bf16x3_no_merge;                                        // GN_WGRAD_NOPIPE, GN_BF16X3_NO_MERGE
+  double bf16x3_min_gflop;                                                   // GN_BF16X3_MIN_GFLOP (default 50)
+};
+const Switches& switches();
+
 // Event-based timing of the MFMA kernels (bench.py roofline leg).  No-ops unless gn_prof_enable(1).
 // Step-varying scalars of a captured hipGraph live in device memory (a by-value kernel argument would be frozen into the graph):
 // rng_base() = the device word every Philox kernel adds to its counter offset (NULL outside graph capture; gn_set_rng_base).
@@ -41,7 +49,7 @@ struct ConvTaps {
   int off[8];
   int widx[8];
   int out_stride, out_off;
-  // merged two-phase launch (stride-2 data gradient, conv_pipe_try_merged): taps with even index j accumulate the output rows
+  // merged two-phase launch (stride-2 data gradient, conv_pipe_run_merged): taps with even index j accumulate the output rows
   // out_stride*m + out_off, taps with odd j the rows out_stride*m + out_off_odd
   int out_off_odd;
 };
@@ -84,9 +92,6 @@ struct WgradArgs {
   double* db_part;  // optional [splits][Cout]: per-split column sums of dy (the bias gradient), written by the blocks of Cin-tile 0
   float* db;        // optional: where wgrad_mfma_dispatch puts the bias gradient when the kernel it selects can sum it on the way
   int db_done;      // set by the dispatcher when db has been written
-  // opt-in conv math (gn_set_conv_math 'bf16x3'): the workspace of the split planes; NULL on the default path (wgrad_bf16x3.hip)
-  void* split_ws;
-  size_t split_ws_bytes;
 };
 
 struct WgradSmallArgs {
@@ -130,9 +135,11 @@ struct ColRedArgs {
 int conv_mfma_dispatch(const ConvArgs& a, hipStream_t s);
 size_t wgrad_workspace_bytes(int B, int M, int Cin, int Cout, int ntaps);
 int wgrad_mfma_dispatch(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s);
-// conv_pipe.hip / wgrad_pipe.hip (hand-scheduled variants selected by the two dispatchers above)
+int wgrad_bf16x3_dispatch(WgradArgs& a, float* dw, void* split_ws, size_t split_ws_bytes, hipStream_t s);
+// conv_pipe.hip / wgrad_pipe.hip (hand-scheduled variants selected by the two dispatchers above; the merged stride-2 data gradient by capi.hip)
 int conv_pipe_try(const ConvArgs& a, bool tall, hipStream_t s, bool* launched);
-int conv_pipe_try_merged(const ConvArgs& a, hipStream_t s, bool* launched);
+bool conv_pipe_merged_supported(const ConvArgs& a);
+int conv_pipe_run_merged(const ConvArgs& a, hipStream_t s);
 void wgrad_pipe_launch(const WgradArgs& a, dim3 grid, bool narrow, hipStream_t s);
 // conv_bf16x3.hip (experimental bf16 x 3 operand-split convolution, opt-in)
 size_t conv_bf16x3_workspace_bytes(int B, int Lin, int Cin, int Cout, int w_taps);
@@ -153,11 +160,11 @@ int conv_wino_s2_run(const ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t s
 void wgrad_split_plan(int B, int M, int Cin, int Cout, int TC, int TN, int* splits, int* chunks_per_split);      // conv_mfma.hip: K-chunks of 32 rows
 bool wgrad_wino_supported(const WgradArgs& a);
 size_t wgrad_wino_workspace_bytes(int B, int M, int Cin, int Cout);
-int wgrad_wino_run(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s);
+int wgrad_wino_run(WgradArgs& a, float* dw, hipStream_t s);
 // wgrad_wino_s2.hip (... of the stride-2 layers: transposed F(2,3) + F(2,2))
 bool wgrad_wino_s2_supported(const WgradArgs& a);
 size_t wgrad_wino_s2_workspace_bytes(int B, int M, int Cin, int Cout);
-int wgrad_wino_s2_run(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s);
+int wgrad_wino_s2_run(WgradArgs& a, float* dw, hipStream_t s);
 // wgrad_bf16x3.hip (the same split for the weight gradient, opt-in)
 size_t wgrad_bf16x3_workspace_bytes(int B, int M, int Cin, int Cout, int in_stride);
 bool wgrad_bf16x3_supported(const WgradArgs& a);

@@ -867,7 +867,7 @@ static int launch_bf16x3_wide3(const ConvArgs& a, int w_taps, void* ws, hipStrea
   return check_launch("conv_bf16x3_wide3");
 }
 
-// Both output phases of a stride-2 data gradient in one launch (a.t as conv_pipe_try_merged takes it: five taps in kernel-tap order, even index -> rows
+// Both output phases of a stride-2 data gradient in one launch (a.t as conv_pipe_run_merged takes it: five taps in kernel-tap order, even index -> rows
 // out_stride * m + out_off, odd index -> out_off_odd).  Returns 0 when the launch does not have the merged form's shape (the caller runs the phases).
 int conv_bf16x3_merged_kind(const ConvArgs& a) {
   if (a.t.ntaps != 5 || a.t.in_stride != 1 || a.t.out_stride != 2 || a.stat_part || a.mask || a.bias || a.M < 192 || a.Cin % 16 || a.Cout % 64) return 0;

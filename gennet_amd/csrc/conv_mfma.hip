@@ -493,10 +493,9 @@ static int launch_conv_impl(const ConvArgs& a, hipStream_t s) {
 template <int WM, int WN, int WAVES_M, int WAVES_N, int KC, int NTAPS>
 static int launch_conv(const ConvArgs& a, hipStream_t s) {
   constexpr int TN = WAVES_N * WN * 32;
-  static const bool no_dma = getenv("GN_CONV_NODMA") != nullptr;       // A/B switch: the register-staged kernel everywhere (tests/test_switches_gpu.py)
   const bool even = (a.Cout % TN == 0) && (a.Cin % KC == 0);                                   // no ragged channel edges
   const bool full = even && ((NTAPS * KC * (TN / 4)) % (64 * WAVES_M * WAVES_N) == 0);       // ... and whole weight items per thread
-  if (even && (NTAPS * KC * (TN / 4)) % 64 == 0 && !no_dma && (size_t)a.Lin * a.Cin * 4 < 0x40000000ull) {
+  if (even && (NTAPS * KC * (TN / 4)) % 64 == 0 && !switches().conv_nodma && (size_t)a.Lin * a.Cin * 4 < 0x40000000ull) {
     if constexpr (KC == 8 && WM == 2 && WN == 2 && NTAPS >= 2) {
       bool launched = false;
       const int rc = conv_pipe_try(a, WAVES_M == 4, s, &launched);     // conv_pipe.hip: hand-scheduled MFMA block, lean epilogue
@@ -683,6 +682,10 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part, float* __res
   }
   reinterpret_cast<float4*>(dw)[i] = s;
 }
+static void wgrad_reduce(const WgradArgs& a, float* dw, int splits, hipStream_t s) {
+  const size_t n = (size_t)a.ntaps * a.Cin * a.Cout;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, a.part, dw, n / 4, splits, n / 4);
+}
 
 // K-splits of the weight gradient: about 2048 blocks in all.  A split is a range of K-chunks (32 rows of one batch element, KT in the kernels);
 // normally whole batch elements (chunks_per_split a multiple of the chunks per element: the partition of every earlier round).  Only when
@@ -743,26 +746,10 @@ static int launch_wgrad(WgradArgs& a, float* dw, hipStream_t s) {
   const int R = a.in_stride * (KT - 1) + (maxoff - minoff) + 1;
   const size_t lds = sizeof(float) * (((size_t)R * TC + 3 & ~(size_t)3) + (size_t)KT * TN);
   dim3 grid(cdiv(a.Cin, TC), cdiv(a.Cout, TN), splits);
-  static const bool no_pipe = getenv("GN_WGRAD_NOPIPE") != nullptr;      // A/B switch: the register-staged weight-gradient kernel everywhere (tests/test_switches_gpu.py)
   bool piped = false;
-  if constexpr (NTAPS == 5 && WNT == 1) {
-    // opt-in split math: six bf16 products per fp32 product (wgrad_bf16x3.hip); same K-split plan, partial slabs and reduce pass as the exact kernel
-    if (a.split_ws && wgrad_bf16x3_supported(a)) {
-      if (wgrad_bf16x3_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.in_stride) > a.split_ws_bytes) {      // never a silent change of arithmetic
-        set_error("weight gradient (bf16x3 math): the split operands need %zu bytes, the workspace has %zu -- raise GENNET_CONV_WS_GB",
-                  wgrad_bf16x3_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.in_stride), a.split_ws_bytes);
-        return GN_EWORKSPACE;
-      }
-      int rc = wgrad_bf16x3_run(a, splits, a.split_ws, a.split_ws_bytes, s);
-      if (rc) return rc;
-      const size_t n = (size_t)NTAPS * a.Cin * a.Cout;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, a.part, dw, n / 4, splits, n / 4);
-      return check_launch("wgrad_reduce");
-    }
-  }
   prof_begin(s);
   if constexpr (NTAPS == 5 && WNT == 1) {
-    if (!no_pipe && a.Cin % TC == 0 && a.Cout % TN == 0 && maxoff - minoff + 1 == NTAPS && (size_t)a.Lin * a.Cin * 4 < 0x40000000ull &&
+    if (!switches().wgrad_nopipe && a.Cin % TC == 0 && a.Cout % TN == 0 && maxoff - minoff + 1 == NTAPS && (size_t)a.Lin * a.Cin * 4 < 0x40000000ull &&
         (size_t)a.M * a.Cout * 4 < 0x40000000ull) {
       // the bias gradient rides along: the blocks of Cin-tile 0 sum the columns of the dy tiles they stage anyway (no separate pass over dy)
       a.db_part = a.db ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.part) + (size_t)splits * NTAPS * a.Cin * a.Cout * sizeof(float)) : nullptr;
@@ -775,8 +762,7 @@ static int launch_wgrad(WgradArgs& a, float* dw, hipStream_t s) {
   prof_end(s, 2.0 * a.B * (double)a.M * NTAPS * a.Cin * a.Cout, 1, 4.0 * ((double)a.B * a.Lin * a.Cin + (double)a.B * a.M * a.Cout + (double)NTAPS * a.Cin * a.Cout));
   int rc = check_launch("wgrad_mfma");
   if (rc) return rc;
-  const size_t n = (size_t)NTAPS * a.Cin * a.Cout;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, a.part, dw, n / 4, splits, n / 4);
+  wgrad_reduce(a, dw, splits, s);
   if (piped && a.db_part) {
     int rc2 = colred_finalize_f32(a.db_part, a.db, (size_t)a.Cout, splits, s);      // db[n] = sum over splits, fp64, fixed order
     if (rc2) return rc2;
@@ -812,6 +798,18 @@ int wgrad_mfma_dispatch(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s)
       set_error("wgrad_mfma: ntaps %d unsupported (1..5)", a.ntaps);
       return GN_EINVAL;
   }
+}
+
+// The opt-in split weight gradient (wgrad_bf16x3.hip, selected in capi.hip): six bf16 products per fp32 product on the exact kernel's K-split
+// plan, partial slabs (ws) and reduce pass; split_ws holds the split operands
+int wgrad_bf16x3_dispatch(WgradArgs& a, float* dw, void* split_ws, size_t split_ws_bytes, hipStream_t s) {
+  int TC, TN, splits;
+  wgrad_tile(a.Cin, a.Cout, a.ntaps, &TC, &TN);
+  wgrad_split_plan(a.B, a.M, a.Cin, a.Cout, TC, TN, &splits, &a.chunks_per_split);
+  int rc = wgrad_bf16x3_run(a, splits, split_ws, split_ws_bytes, s);
+  if (rc) return rc;
+  wgrad_reduce(a, dw, splits, s);
+  return check_launch("wgrad_reduce");
 }
 
 }  // namespace gn

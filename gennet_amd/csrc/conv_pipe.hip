@@ -467,12 +467,11 @@ static int launch_conv_pipe(const ConvArgs& a, hipStream_t s) {
     set_error("conv_mfma_pipe: bad grid %zu", blocks);
     return GN_EINVAL;
   }
-  static const bool no_patch = getenv("GN_CONV_NOPATCH") != nullptr;          // A/B switch
   int patch = -1;
   {
     const int pn = n_tiles % 8 == 0 ? 3 : (n_tiles == 4 ? 2 : -1);
     const int ng = pn >= 0 ? n_tiles >> pn : 0;
-    if (!no_patch && pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0) patch = __builtin_ctz(ng) | (pn << 8);
+    if (!switches().conv_nopatch && pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0) patch = __builtin_ctz(ng) | (pn << 8);
   }
   prof_begin(s);
   hipLaunchKernelGGL((conv_mfma_pipe_kernel<WAVES_M, WAVES_N, NTAPS, IS, KC, WN, SPAN, MERGE>), dim3((unsigned)blocks), dim3(64 * WAVES_M * WAVES_N * (MERGE == 2 ? 2 : 1)), lds, s, a, m_tiles, n_tiles,
@@ -488,7 +487,6 @@ static int launch_conv_pipe(const ConvArgs& a, hipStream_t s) {
 // Selection for conv_mfma_dispatch (conv_mfma.hip): tile (tall 256 x 64 or square 128 x 128), tap count, input stride.  *launched stays
 // false when the shape is outside what the pipelined kernel covers (the caller then runs the plain DMA kernel).
 int conv_pipe_try(const ConvArgs& a, bool tall, hipStream_t s, bool* launched) {
-  static const bool no_pipe = getenv("GN_CONV_NOPIPE") != nullptr;      // A/B switch
   *launched = false;
   const int nt = a.t.ntaps;
   int minoff = a.t.off[0], maxoff = a.t.off[0];
@@ -496,7 +494,7 @@ int conv_pipe_try(const ConvArgs& a, bool tall, hipStream_t s, bool* launched) {
     minoff = std::min(minoff, a.t.off[j]);
     maxoff = std::max(maxoff, a.t.off[j]);
   }
-  if (no_pipe || nt < 2 || nt > 5 || maxoff - minoff + 1 > nt || (size_t)a.Ly * a.Cout * 4 >= 0x40000000ull ||
+  if (switches().conv_nopipe || nt < 2 || nt > 5 || maxoff - minoff + 1 > nt || (size_t)a.Ly * a.Cout * 4 >= 0x40000000ull ||
       (size_t)a.Lin * a.Cin * 4 >= 0x40000000ull)      // the input descriptor's byte count and its out-of-range sentinel offset 0x40000000 must stay apart
     return GN_OK;
   if (a.t.in_stride != 1 && !(a.t.in_stride == 2 && nt == 5)) return GN_OK;
@@ -513,10 +511,9 @@ int conv_pipe_try(const ConvArgs& a, bool tall, hipStream_t s, bool* launched) {
   // What fills the chip is both at once: NARROW waves (64 x 32 each, pipe_group_n) in SMALLER blocks of 64 columns -- 8, 4 or 2 waves for 256,
   // 128 or 64 rows -- so that a launch with fewer than two 64 x 64 wave tiles per SIMD gets at least one block per CU (256 blocks: 1.62 /
   // 4.28; requiring two, 512 blocks, 1.71 / 4.54; 128 blocks 1.78 / 4.67), and every block still spreads over the CU's SIMDs.
-  static const bool no_narrow = getenv("GN_CONV_NONARROW") != nullptr;          // A/B switch
   constexpr int narrow_below = 2048;
   const size_t wave_tiles = (size_t)a.B * (size_t)((a.M + 63) / 64) * (size_t)(a.Cout / 64);
-  const bool narrow_wave = !no_narrow && a.Cout % 64 == 0 && wave_tiles < (size_t)narrow_below;
+  const bool narrow_wave = !switches().conv_nonarrow && a.Cout % 64 == 0 && wave_tiles < (size_t)narrow_below;
   int nwm = 4;
   if (narrow_wave) {
     auto blocks_of = [&](int wm_) { return (size_t)a.B * (size_t)((a.M + 64 * wm_ - 1) / (64 * wm_)) * (size_t)(a.Cout / 64); };
@@ -553,26 +550,25 @@ int conv_pipe_try(const ConvArgs& a, bool tall, hipStream_t s, bool* launched) {
 // (phase of tap kk alternates with kk), so the block stages the slab once and every K-chunk carries all five taps: narrow waves with two
 // accumulator sets chosen by tap parity (PipeChunk::run_m, two epilogues), or twice the waves with one phase each (PipeChunk::run_p).  Two separate launches of 3 and 2 taps each walk every channel
 // chunk; at the script's own batch 8 that made the data gradient of a stride-2 layer twice as slow as its forward.
-// a.t: ntaps 5 in kernel-tap order (even index <-> rows out_stride*m + out_off, odd index <-> out_off_odd), offsets spanning 3 rows.
-int conv_pipe_try_merged(const ConvArgs& a, hipStream_t s, bool* launched) {
-  // A/B switches: the merged kernel is a member of the pipelined LDS-DMA family, so every switch that takes that family out (to run and test
-  // the fallback kernels) takes it out too
-  static const bool off = getenv("GN_CONV_NOMERGE") != nullptr || getenv("GN_CONV_NOPIPE") != nullptr || getenv("GN_CONV_NODMA") != nullptr;
-  constexpr int merge_below = 2048;
-  *launched = false;
-  if (off || a.t.ntaps != 5 || a.t.in_stride != 1 || a.t.out_stride != 2 || a.stat_part || a.mask || a.bias) return GN_OK;
+// a.t: ntaps 5 in kernel-tap order (even index <-> rows out_stride*m + out_off, odd index <-> out_off_odd), offsets spanning 3 rows.  Selected
+// in capi.hip (select_dgrad); the A/B switches that take the pipelined family out take this member out too.
+bool conv_pipe_merged_supported(const ConvArgs& a) {
+  if (a.t.ntaps != 5 || a.t.in_stride != 1 || a.t.out_stride != 2 || a.stat_part || a.mask || a.bias) return false;
   int minoff = a.t.off[0], maxoff = a.t.off[0];
   for (int j = 1; j < 5; ++j) {
     minoff = std::min(minoff, a.t.off[j]);
     maxoff = std::max(maxoff, a.t.off[j]);
   }
-  if (maxoff - minoff + 1 > 3 || a.Cin % 8 || a.Cout % 64 || (size_t)a.Ly * a.Cout * 4 >= 0x40000000ull || (size_t)a.Lin * a.Cin * 4 >= 0x40000000ull) return GN_OK;
+  if (maxoff - minoff + 1 > 3 || a.Cin % 8 || a.Cout % 64 || (size_t)a.Ly * a.Cout * 4 >= 0x40000000ull || (size_t)a.Lin * a.Cin * 4 >= 0x40000000ull) return false;
+  constexpr int merge_below = 2048;
   const size_t wave_tiles = (size_t)a.B * (size_t)((a.M + 63) / 64) * (size_t)(a.Cout / 64) * 2;       // 64 x 64 tiles of both phases
-  if (wave_tiles >= (size_t)merge_below) return GN_OK;
+  return wave_tiles < (size_t)merge_below;
+}
+
+int conv_pipe_run_merged(const ConvArgs& a, hipStream_t s) {
   auto blocks_of = [&](int wm_) { return (size_t)a.B * (size_t)((a.M + 64 * wm_ - 1) / (64 * wm_)) * (size_t)(a.Cout / 64); };
   int nwm = 4;
   while (nwm > 1 && blocks_of(nwm) < 256) nwm >>= 1;
-  *launched = true;
   // 256-row blocks: 8 narrow waves, each both phases (two accumulator sets); smaller blocks: twice the waves, each ONE phase and only the taps
   // of its parity -- the merged wave is a 64 x 64 x 2-phase tile, which left half the SIMDs idle at batch 8.  Measured at batch 8 (us per
   // launch, both-phase waves -> phase-split waves): PE q 512 -> 1024 data gradient 162 -> 111 (its forward: 94), PE q 256 -> 512 84 -> 58,

@@ -374,7 +374,7 @@ bool wgrad_bf16x3_supported(const WgradArgs& a) {
   return maxoff - minoff == 4 && minoff <= 0 && minoff >= -4;
 }
 
-// The split passes and the kernel; the caller (launch_wgrad, conv_mfma.hip) owns the K-split plan (a.chunks_per_split, splits) and the reduce pass.
+// The split passes and the kernel; the caller (wgrad_bf16x3_dispatch, conv_mfma.hip) owns the K-split plan (a.chunks_per_split, splits) and the reduce pass.
 int wgrad_bf16x3_run(const WgradArgs& a_in, int splits, void* ws, size_t ws_bytes, hipStream_t s) {
   WgradArgs a = a_in;
   const int xcd_order = splits % 8 == 0;

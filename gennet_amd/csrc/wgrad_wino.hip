@@ -280,17 +280,14 @@ size_t wgrad_wino_workspace_bytes(int B, int M, int Cin, int Cout) {
   return (size_t)s * 6 * Cin * Cout * sizeof(float);
 }
 
-int wgrad_wino_run(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s) {
+// a.part: wgrad_wino_workspace_bytes (checked by the caller, gn_conv1d_wgrad)
+int wgrad_wino_run(WgradArgs& a, float* dw, hipStream_t s) {
   if (!wgrad_wino_supported(a)) {
     set_error("wgrad_wino: unsupported shape");
     return GN_EINVAL;
   }
   int splits;
   wgrad_split_plan(a.B, a.M, a.Cin, a.Cout, 64, 64, &splits, &a.chunks_per_split);
-  if (ws_bytes < (size_t)splits * 6 * a.Cin * a.Cout * sizeof(float)) {
-    set_error("wgrad_wino: workspace too small");
-    return GN_EWORKSPACE;
-  }
   const int cpb = (a.M + 31) / 32;
   constexpr size_t lds = 3 * sizeof(float) * (4 * 2 * 20 * 16 + 4 * 2 * 16 * 16);
   dim3 grid(a.Cin / 64, a.Cout / 64, splits);

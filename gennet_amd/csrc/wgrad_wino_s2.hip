@@ -270,17 +270,14 @@ size_t wgrad_wino_s2_workspace_bytes(int B, int M, int Cin, int Cout) {
   return (size_t)s * 7 * Cin * Cout * sizeof(float);
 }
 
-int wgrad_wino_s2_run(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s) {
+// a.part: wgrad_wino_s2_workspace_bytes (checked by the caller, gn_conv1d_wgrad)
+int wgrad_wino_s2_run(WgradArgs& a, float* dw, hipStream_t s) {
   if (!wgrad_wino_s2_supported(a)) {
     set_error("wgrad_wino_s2: unsupported shape");
     return GN_EINVAL;
   }
   int splits, cpb;
   s2_plan(a.B, a.M, a.Cin, a.Cout, &splits, &a.chunks_per_split, &cpb);
-  if (ws_bytes < (size_t)splits * 7 * a.Cin * a.Cout * sizeof(float)) {
-    set_error("wgrad_wino_s2: workspace too small");
-    return GN_EWORKSPACE;
-  }
   constexpr size_t lds = 3 * sizeof(float) * (4 * 4 * 12 * 16 + 4 * 2 * 8 * 16);
   dim3 grid(a.Cin / 64, a.Cout / 64, splits);
   prof_begin(s);

@@ -39,7 +39,7 @@ def device():
         _DEVICE = torch.device('cuda', idx)
         # conv arithmetic (ops.set_conv_math): transform-domain fp32 for the unit-stride 5-tap layers by default; GENNET_CONV_MATH=fp32 keeps every
         # launch on the direct kernels, =bf16x3 is the opt-in operand-split experiment
-        ops.set_conv_math(ops.default_conv_math(), float(os.environ.get('GENNET_CONV_WS_GB', '7')), _DEVICE)
+        ops.set_conv_math(device=_DEVICE)
     return _DEVICE
 
 
@@ -228,7 +228,7 @@ class StepGraph(object):
         self.copied = torch.cuda.Event()
         self._copied_once = False
         self.outputs = None
-        self.scratch = []                  # every ops.workspace() buffer handed out during capture: the graph holds their addresses
+        self.scratch = []                  # every ops.workspace() buffer handed out during capture and the conv-math buffer: the graph holds their addresses
 
     def slot(self, fmt, provider):
         """Reserve one 8-byte slot holding a scalar of struct format `fmt` ('f', 'i', 'Q'); provider() -> value is called before every replay."""
@@ -256,6 +256,8 @@ class StepGraph(object):
             device_rng().offset += self.rng_taken
             return base
         base = self.slot('Q', rng_base)
+        if ops.conv_math_workspace() is not None:
+            keep(ops.conv_math_workspace())
         self.graph = torch.cuda.CUDAGraph()
         _CAPTURE = self
         ops.set_rng_base(base.ptr)

@@ -350,7 +350,8 @@ def conv_fold_bn(w, b, scale, shift):
     return w2, b2
 
 
-_CONV_MATH_WS = [None]
+_CONV_MATH_WS = {}             # (device, mode) -> the buffer gn_set_conv_math was handed; kept, so switching modes allocates nothing
+_CONV_MATH_CUR = [None]        # the buffer of the current mode (StepGraph.capture keeps it alive: a captured graph holds its address)
 
 
 def default_conv_math():
@@ -359,34 +360,49 @@ def default_conv_math():
     return os.environ.get('GENNET_CONV_MATH', 'wino')
 
 
-WINO_WS_BYTES = 64 << 20       # transformed kernel of one launch: 6 * Cin * Cout * 4 bytes (25 MB for the generator's 512 -> 1024 layer)
+def default_conv_ws_gb():
+    """The opt-in split's workspace the engine starts with: GENNET_CONV_WS_GB, 7 when unset."""
+    import os
+    return float(os.environ.get('GENNET_CONV_WS_GB', '7'))
 
 
-def set_conv_math(mode=None, workspace_gb=7.0, device=None):
-    """How the MFMA convolutions compute (process-wide, csrc/capi.hip conv_dispatch):
-    'wino' (the engine's default): the unit-stride 5-tap Conv1D forward / data-gradient launches with Cin >= 32, Cin % 8 == 0 and Cout % 64 == 0 run in the
-        transform domain (Cook-Toom F(2,5), csrc/conv_wino.hip: 6 fp32 multiplies per two outputs instead of 10, every product an exact fp32 fma on the fp32
-        matrix instruction); everything else on the direct kernels.  Chosen by the layer's shape alone (never the batch size).
+WINO_WS_BYTES = 64 << 20       # the library's limit on a transformed kernel (csrc/capi.hip: wino only where it fits); gn_set_conv_math(2) needs it
+
+
+def set_conv_math(mode=None, workspace_gb=None, device=None):
+    """How the MFMA convolutions compute (process-wide; which launches each mode reaches: csrc/capi.hip, select_conv and the table above it):
+    'wino' (the engine's default): transform-domain fp32 on the 5-tap layers the selector admits, the direct kernels elsewhere.
     'fp32': the direct exact-fp32 MFMA kernels everywhere (results bit-identical to a k-ordered fmaf chain).
-    'bf16x3': opt-in experiment -- the launches with at least 256 channels on either side run on the bf16 matrix cores with 3-way split operands
-        (csrc/conv_bf16x3.hip, csrc/wgrad_bf16x3.hip); workspace_gb must hold the split operands of the largest such launch."""
+    'bf16x3': opt-in experiment -- the large launches run on the bf16 matrix cores with 3-way split operands; workspace_gb must hold the split
+        operands of the largest such launch.
+    No arguments: the mode and workspace the engine started with (default_conv_math, default_conv_ws_gb).  One buffer per (device, mode), reused:
+    the 'wino' buffer is never replaced, the 'bf16x3' one only by a larger request."""
     dev = device or torch.device('cuda', torch.cuda.current_device())
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
     if mode is None:
         mode = default_conv_math()
+    if workspace_gb is None:
+        workspace_gb = default_conv_ws_gb()
+    if mode not in ('fp32', 'wino', 'bf16x3'):
+        raise ValueError('conv math %r (wino | fp32 | bf16x3)' % (mode,))
     if mode == 'fp32':
         _lib.call('gn_set_conv_math', 0, None, 0)
-        _CONV_MATH_WS[0] = None
+        _CONV_MATH_CUR[0] = None
         return
-    if mode == 'wino':
-        ws = torch.empty(WINO_WS_BYTES, dtype=torch.uint8, device=dev)
-        _lib.call('gn_set_conv_math', 2, _p(ws), ws.numel())
-        _CONV_MATH_WS[0] = ws
-        return
-    if mode != 'bf16x3':
-        raise ValueError('conv math %r (wino | fp32 | bf16x3)' % (mode,))
-    ws = torch.empty(int(workspace_gb * (1 << 30)), dtype=torch.uint8, device=dev)
-    _lib.call('gn_set_conv_math', 1, _p(ws), ws.numel())
-    _CONV_MATH_WS[0] = ws
+    nbytes = WINO_WS_BYTES if mode == 'wino' else int(workspace_gb * (1 << 30))
+    key = (dev.type, dev.index, mode)
+    ws = _CONV_MATH_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _CONV_MATH_WS[key] = ws
+    _lib.call('gn_set_conv_math', 2 if mode == 'wino' else 1, _p(ws), nbytes)
+    _CONV_MATH_CUR[0] = ws
+
+
+def conv_math_workspace():
+    """The device buffer the current conv math works in (None under 'fp32')."""
+    return _CONV_MATH_CUR[0]
 
 
 import contextlib

@@ -126,3 +126,32 @@ def test_a_captured_graph_keeps_its_scratch_buffer_alive():
     assert all(j.data_ptr() != old_ptr for j in junk)                    # ... but the graph still owns it
     got += [step() for _ in range(steps - 3)]
     assert got == eager, (got, eager)
+
+
+def test_a_captured_graph_survives_conv_math_switches():
+    """ops.set_conv_math allocated a new conv-math workspace on every call -- also in the `finally` of ops.conv_math() -- while a captured
+    graph kept the raw address of the old one.  Each mode's buffer is now allocated once and reused, and StepGraph.capture keeps the current one
+    alive: after the math is toggled, torch's cache emptied and freed memory overwritten, replays still equal the eager loop bit for bit and
+    write nothing outside what the graph owns."""
+    import gc
+    from gennet_amd import bbh, engine, ops
+    n_pix, B, steps = 256, 8, 7
+    nets, bank, _ = _setup(n_pix, 17)
+    eager = [bbh.pe_train_step(nets.signal_pe, bank, B) for _ in range(steps)]
+    nets, bank, _ = _setup(n_pix, 17)
+    step = bbh.GraphedPEStep(nets.signal_pe, bank, B)
+    got = [step() for _ in range(3)]                                     # eager, capture + replay, replay
+    ws = ops.conv_math_workspace()
+    assert ws is not None and any(b is ws for b in step.sg.scratch)
+    for _ in range(steps - 3):
+        for _ in range(3):
+            with ops.conv_math('fp32'):
+                assert ops.conv_math_workspace() is None
+            assert ops.conv_math_workspace() is ws                       # switching back allocated nothing
+        gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
+        junk = [torch.full((ws.numel() // 4,), float('nan'), device=engine.device()) for _ in range(2)]      # would land on a freed buffer
+        got.append(step())
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(j).all()) for j in junk)
+        del junk
+    assert got == eager, (got, eager)

@@ -44,6 +44,31 @@ def test_no_cpu_fallback_in_product_path():
     assert [m.start() > bench.index('def cpu_baseline(') and m.start() < bench.index('def free_port(') for m in re.finditer(r'(from|import)\s+oracle', bench)] == [True]
 
 
+def test_conv_math_workspace_rules_at_the_c_abi():
+    """Host-only C-ABI calls (the workspace is never dereferenced): gn_set_conv_math(2, ...) refuses a workspace smaller than the 64 MiB the
+    transform-domain kernels need, with GN_EWORKSPACE and the previous math left in place; the weight-gradient workspace query asks the same
+    selector as the launch, so under math 2 it grows by the transform-domain slabs exactly for the layers whose transformed kernel (6 x Cin x Cout
+    floats at stride 1, 7 at stride 2) fits in 64 MiB."""
+    from gennet_amd import _lib, ops
+    L = _lib.lib()
+    fake = ctypes.c_void_p(1 << 20)
+
+    def query(Cin, Cout, stride):
+        return _lib.size('gn_conv1d_wgrad_workspace', 2, 64, Cin, Cout, 5, stride, 64 // stride)
+
+    shapes = [(64, 128, 1), (1024, 2688, 1), (1024, 2752, 1), (1024, 2304, 2), (1024, 2368, 2)]
+    direct = [query(*s) for s in shapes]
+    assert L.gn_set_conv_math(2, fake, ctypes.c_size_t(ops.WINO_WS_BYTES - 1)) == -3            # GN_EWORKSPACE
+    assert b'workspace' in L.gn_last_error()
+    assert [query(*s) for s in shapes] == direct                                                # still math 0
+    try:
+        _lib.call('gn_set_conv_math', 2, fake, ops.WINO_WS_BYTES)
+        wino = [query(*s) for s in shapes]
+    finally:
+        _lib.call('gn_set_conv_math', 0, None, 0)
+    assert [w > d for w, d in zip(wino, direct)] == [True, True, False, True, False], (wino, direct)
+
+
 def test_graphs_fusion_plan_and_param_counts():
     from gennet_amd import bbh
     n_pix = 2048

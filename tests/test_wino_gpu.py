@@ -201,6 +201,68 @@ def test_dispatch_leaves_everything_else_on_the_direct_kernels():
         ops.prof_enable(False)
 
 
+@pytest.mark.parametrize("Cin,Cout,stride", [(1024, 2752, 1), (1024, 2368, 2)])
+def test_a_transformed_kernel_above_64_mib_keeps_the_whole_layer_on_the_direct_kernels(Cin, Cout, stride):
+    """The transform-domain families take a layer only if its transformed kernel (6 x Cin x Cout floats, 7 at stride 2) fits in 64 MiB, the same
+    rule for forward, data gradient and weight gradient (csrc/capi.hip select_conv / select_dgrad / select_wgrad).  Just above it all three run on
+    the direct kernels and equal the 'fp32' math bit for bit; 64 output channels fewer, the forward takes the transform domain."""
+    from gennet_amd import ops
+    pts = 6 if stride == 1 else 7
+    assert pts * Cin * (Cout - 64) * 4 <= ops.WINO_WS_BYTES < pts * Cin * Cout * 4
+    dev = torch.device('cuda:0')
+    B, L = 2, 64
+    Lout, pl = ops.conv_geometry(L, 5, stride, 'same')
+    x = ops.fill_normal((B, L, Cin), 0.0, 1.0, 31, 0, dev)
+    w = ops.fill_normal((5, Cin, Cout), 0.0, 0.02, 32, 0, dev)
+    dy = ops.fill_normal((B, Lout, Cout), 0.0, 1.0, 33, 0, dev)
+
+    def run():
+        ops.prof_reset()
+        out = [ops.conv1d_fwd(x, w, None, stride, pl, Lout), ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w), L, stride, pl)]
+        out += list(ops.conv1d_wgrad(x, dy, 5, stride, pl))
+        return [t.cpu().numpy() for t in out], [launches(k) for k in range(9)]
+
+    ops.prof_enable(True)
+    try:
+        with ops.conv_math('wino'):
+            got, n = run()
+            ops.prof_reset()
+            ops.conv1d_fwd(x, w[:, :, :Cout - 64].contiguous(), None, stride, pl, Lout)
+            n_fit = launches(5 if stride == 1 else 7)
+        with ops.conv_math('fp32'):
+            ref, n_ref = run()
+    finally:
+        ops.prof_enable(False)
+    assert n[5:] == [0, 0, 0, 0] and n == n_ref and n[0] >= 2 and n[1] == 1, (n, n_ref)
+    assert n_fit == 1
+    for a, b in zip(got, ref):
+        assert np.array_equal(a, b)
+
+
+def test_a_weight_gradient_workspace_too_small_for_its_kernel_is_an_error():
+    """The transform-domain weight gradient used to fall back to the direct kernel when the caller's workspace could not hold its slabs; the kernel
+    is now chosen by the layer's shape alone, and a workspace that holds only what the direct kernel would need is GN_EWORKSPACE (C ABI)."""
+    from gennet_amd import _lib, ops
+    dev = torch.device('cuda:0')
+    B, L, Cin, Cout = 2, 256, 64, 128
+    x = ops.fill_normal((B, L, Cin), 0.0, 1.0, 41, 0, dev)
+    dy = ops.fill_normal((B, L, Cout), 0.0, 1.0, 42, 0, dev)
+    dw = torch.empty((5, Cin, Cout), dtype=torch.float32, device=dev)
+    db = torch.empty((Cout,), dtype=torch.float32, device=dev)
+    args = (B, L, Cin, Cout, 5, 1, L)
+    with ops.conv_math('fp32'):
+        n_direct = _lib.size('gn_conv1d_wgrad_workspace', *args)
+    with ops.conv_math('wino'):
+        n_wino = _lib.size('gn_conv1d_wgrad_workspace', *args)
+        assert n_wino > n_direct
+        ws = torch.empty(n_wino, dtype=torch.uint8, device=dev)
+        with pytest.raises(_lib.GennetHipError, match='workspace'):
+            _lib.call('gn_conv1d_wgrad', ops._p(x), ops._p(dy), ops._p(dw), ops._p(db), ops._p(ws), n_direct, B, L, Cin, Cout, 5, 1, 2, L, ops._stream())
+        _lib.call('gn_conv1d_wgrad', ops._p(x), ops._p(dy), ops._p(dw), ops._p(db), ops._p(ws), n_wino, B, L, Cin, Cout, 5, 1, 2, L, ops._stream())
+        dw_ref, db_ref = ops.conv1d_wgrad(x, dy, 5, 1, 2)
+    assert torch.equal(dw, dw_ref) and torch.equal(db, db_ref)
+
+
 # ---------------------------------------------------------------------------------------------- stride-2 layers: F(2,3) + F(2,2) (csrc/conv_wino_s2.hip)
 S2_CASES = [
     # B, L, Cin, Cout, padding          (pad_left parity decides which output phase the 3-tap half of the data gradient writes and where the 2-tap rows start)
