@@ -158,4 +158,39 @@ __device__ __forceinline__ void pipe_epilogue_dispatch(const ConvArgs& a, const 
 #undef GN_EPI
 }
 
+// Block -> tile of the tiled conv launches (conv_pipe.hip, conv_wino.hip, conv_wino_s2.hip).  Plain order is (slab, column tile) with the column tile fastest: block i runs on
+// XCD i mod 8, so every XCD meets every input slab and the slab crosses the fabric 8 times.  Patch order (patch >= 0) hands each XCD, out of every 512
+// consecutive blocks, the 64 blocks of ONE patch of (64 / PN) slabs x PN column tiles (PN = 8, or 4 when there are only 4 column tiles) -- the set an
+// XCD has in flight at two blocks per CU -- so its L2 serves each slab chunk to PN blocks and each weight chunk to 64 / PN.
+// patch = log2(column tiles / PN) | log2(PN) << 8.  Blocks past the last whole 512 keep the plain order (both orders cover the same leading slabs).
+// Measured on G 512 -> 1024 (conv_pipe.hip): FETCH_SIZE -25 %, +0.3 % on the step.  A slab is m_tiles row tiles of one batch element.
+struct BlockTile {
+  int n_tile, m_tile, b;
+};
+__device__ __forceinline__ BlockTile xcd_block_tile(int patch, int m_tiles, int n_tiles) {
+  const int bid = blockIdx.x;
+  int n_lin, slab;
+  if (patch >= 0 && bid < (int)(gridDim.x & ~511u)) {
+    const int ps = patch & 255, pn = patch >> 8;
+    const int r = bid & 511, p = (bid >> 9) * 8 + (r & 7), idx = r >> 3;
+    slab = ((p >> ps) << (6 - pn)) + (idx >> pn);
+    n_lin = ((p & ((1 << ps) - 1)) << pn) + (idx & ((1 << pn) - 1));
+  } else {
+    n_lin = bid % n_tiles;
+    slab = bid / n_tiles;
+  }
+  BlockTile t;
+  t.n_tile = __builtin_amdgcn_readfirstlane(n_lin);
+  const int slab_s = __builtin_amdgcn_readfirstlane(slab);
+  t.m_tile = slab_s % m_tiles;
+  t.b = slab_s / m_tiles;
+  return t;
+}
+// the patch argument of a launch with n_tiles column tiles; -1 (plain order) when no patch shape fits
+static inline int xcd_patch(int n_tiles) {
+  const int pn = n_tiles % 8 == 0 ? 3 : (n_tiles == 4 ? 2 : -1);
+  const int ng = pn >= 0 ? n_tiles >> pn : 0;
+  return pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0 ? __builtin_ctz(ng) | (pn << 8) : -1;
+}
+
 }  // namespace gn

@@ -267,26 +267,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (MERGE == 2 ? 2 : 1), (64 
   const int wave = MERGE == 2 ? wave_all % (WAVES_M * WAVES_N) : wave_all;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int i32 = lane & 31, h = lane >> 5;
-  // block -> tile.  Plain order is (slab, column tile) with the column tile fastest: block i runs on XCD i mod 8, so every XCD meets
-  // every input slab and the slab crosses the fabric 8 times.  Patch order (patch >= 0) hands each XCD, out of every 512 consecutive
-  // blocks, the 64 blocks of ONE patch of (64 / PN) slabs x PN column tiles (PN = 8, or 4 when there are only 4 column tiles) -- the
-  // set an XCD has in flight at two blocks per CU -- so its L2 serves each slab chunk to PN blocks and each weight chunk to 64 / PN.
-  // patch = log2(column tiles / PN) | log2(PN) << 8.  Blocks past the last whole 512 keep the plain order (both orders cover the
-  // same leading slabs).  Measured on G 512 -> 1024: FETCH_SIZE -25 %, +0.3 % on the step.
-  const int bid = blockIdx.x;
-  int n_lin, slab;
-  if (patch >= 0 && bid < (int)(gridDim.x & ~511u)) {
-    const int ps = patch & 255, pn = patch >> 8;
-    const int r = bid & 511, p = (bid >> 9) * 8 + (r & 7), idx = r >> 3;
-    slab = ((p >> ps) << (6 - pn)) + (idx >> pn);
-    n_lin = ((p & ((1 << ps) - 1)) << pn) + (idx & ((1 << pn) - 1));
-  } else {
-    n_lin = bid % n_tiles;
-    slab = bid / n_tiles;
-  }
-  const int n_tile = __builtin_amdgcn_readfirstlane(n_lin);
-  const int m_tile = __builtin_amdgcn_readfirstlane(slab % m_tiles);
-  const int b = __builtin_amdgcn_readfirstlane(slab / m_tiles);
+  const BlockTile bt = xcd_block_tile(patch, m_tiles, n_tiles);
+  const int n_tile = bt.n_tile, m_tile = bt.m_tile, b = bt.b;
   const int m0 = m_tile * TM, n0 = n_tile * TN;
 
   int minoff = a.t.off[0];
@@ -467,12 +449,7 @@ static int launch_conv_pipe(const ConvArgs& a, hipStream_t s) {
     set_error("conv_mfma_pipe: bad grid %zu", blocks);
     return GN_EINVAL;
   }
-  int patch = -1;
-  {
-    const int pn = n_tiles % 8 == 0 ? 3 : (n_tiles == 4 ? 2 : -1);
-    const int ng = pn >= 0 ? n_tiles >> pn : 0;
-    if (!switches().conv_nopatch && pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0) patch = __builtin_ctz(ng) | (pn << 8);
-  }
+  const int patch = switches().conv_nopatch ? -1 : xcd_patch(n_tiles);
   prof_begin(s);
   hipLaunchKernelGGL((conv_mfma_pipe_kernel<WAVES_M, WAVES_N, NTAPS, IS, KC, WN, SPAN, MERGE>), dim3((unsigned)blocks), dim3(64 * WAVES_M * WAVES_N * (MERGE == 2 ? 2 : 1)), lds, s, a, m_tiles, n_tiles,
                      patch);

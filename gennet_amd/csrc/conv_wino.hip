@@ -64,21 +64,8 @@ __global__ void wino_u_kernel(const float* __restrict__ w, float* __restrict__ U
 //               the previous barrier), slot 0 also this lane's six raw row fragments of the NEXT chunk; a counted lgkmcnt retires exactly what the slot
 //               consumes (LDS returns in order);
 //   slots 12, 24, 36 carry the 14 transform instructions of the next chunk in three runs; the staging pieces of chunk + 2 sit behind slots 1, 3, ...
+// (wino_slot, wino_slot_rb: wino_common.h)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wino_slot(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b) : "memory");
-}
-template <int O, int WAIT>
-__device__ __forceinline__ void wino_slot_rb(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b) {
-  asm volatile(
-      "ds_read_b128 %1, %5 offset:%6\n\t"
-      "ds_read_b128 %2, %5 offset:%7\n\t"
-      "s_waitcnt lgkmcnt(%8)\n\t"
-      "v_mfma_f32_16x16x4_f32 %0, %3, %4, %0"
-      : "+v"(c), "=&v"(nb0), "=&v"(nb1)
-      : "v"(a), "v"(b), "v"(addr_b), "i"(O), "i"(O + 1024), "i"(WAIT)
-      : "memory");
-}
 // ... and the raw fragments of the next chunk (slot 0); this point's U values were read across the barrier: the wait retires them
 template <int O, int OP1>
 __device__ __forceinline__ void wino_slot_rba(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b, f32x2 (&d)[6], unsigned addr_a) {
@@ -161,21 +148,8 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n16 = lane & 15, kq = lane >> 4;
-  // block -> tile: the XCD patch order of conv_pipe.hip
-  const int bid = blockIdx.x;
-  int n_lin, slab;
-  if (patch >= 0 && bid < (int)(gridDim.x & ~511u)) {
-    const int ps = patch & 255, pn = patch >> 8;
-    const int r = bid & 511, p = (bid >> 9) * 8 + (r & 7), idx = r >> 3;
-    slab = ((p >> ps) << (6 - pn)) + (idx >> pn);
-    n_lin = ((p & ((1 << ps) - 1)) << pn) + (idx & ((1 << pn) - 1));
-  } else {
-    n_lin = bid % n_tiles;
-    slab = bid / n_tiles;
-  }
-  const int n_tile = __builtin_amdgcn_readfirstlane(n_lin);
-  const int m_tile = __builtin_amdgcn_readfirstlane(slab % m_tiles);
-  const int b = __builtin_amdgcn_readfirstlane(slab / m_tiles);
+  const BlockTile bt = xcd_block_tile(patch, m_tiles, n_tiles);  // the XCD patch order of conv_epilogue.h
+  const int n_tile = bt.n_tile, m_tile = bt.m_tile, b = bt.b;
   const int t0 = m_tile * TT, n0 = n_tile * TN;
 
   f32x4 acc[NP][4];
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
     const char* sb = reinterpret_cast<const char*>(smem);
 #pragma unroll
     for (int j = 0; j < 6; ++j) d[j] = *reinterpret_cast<const f32x2*>(sb + (base_a - lds0) + (j & 1) * RPER * 32 + (j >> 1) * 32);
-    wino_bt_all(d, V0, tt, k15, km15);
+    wino_run<0, kWinoPieces>(d, V0, tt, k15, km15);
     Bq[0][0] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0));
     Bq[0][1] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0) + 1024);
   }
@@ -347,12 +321,7 @@ static int launch_conv_wino(const ConvArgs& a, const float* U, int off0, hipStre
     set_error("conv_wino: bad grid %zu", blocks);
     return GN_EINVAL;
   }
-  int patch = -1;
-  {
-    const int pn = n_tiles % 8 == 0 ? 3 : (n_tiles == 4 ? 2 : -1);
-    const int ng = pn >= 0 ? n_tiles >> pn : 0;
-    if (pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0) patch = __builtin_ctz(ng) | (pn << 8);
-  }
+  const int patch = xcd_patch(n_tiles);             // (GN_CONV_NOPATCH is conv_pipe.hip's switch: these kernels always take the patch order)
   prof_begin(s);
   hipLaunchKernelGGL((conv_wino_kernel<WAVES_M, ABL>), dim3((unsigned)blocks), dim3(64 * WAVES_M), lds, s, a, U, off0, m_tiles, n_tiles, patch);
   // flop = what the kernel EXECUTES on the matrix pipe: 6 multiplies per output pair and channel pair, 0.6 of the convolution's algorithmic count

@@ -4,7 +4,7 @@
 // A stride-2 5-tap convolution is a 3-tap plus a 2-tap UNIT-stride convolution on the even and the odd input rows,
 //     y[t] = a[t] w0 + a[t+1] w2 + a[t+2] w4 + b[t] w1 + b[t+1] w3,        a[n] = x[2n + off0], b[n] = x[2n + 1 + off0],
 // and its data gradient is two unit-stride phases of 3 and 2 taps over the same dy rows.  Cook-Toom F(2,3) on points {0, 1, -1, inf} and F(2,2) on {0, 1, inf}:
-// 4 + 3 = SEVEN multiplies per output pair instead of ten, with input transforms made of additions only (six packed instructions against F(2,5)'s eighteen):
+// 4 + 3 = SEVEN multiplies per output pair instead of ten, with input transforms made of additions only (seven packed instructions against F(2,5)'s fourteen; wino_common.h: s2_piece):
 //     v0 = a0 - a2, v1 = a1 + a2, v2 = a2 - a1, v3 = a1 - a3 | v4 = b0 - b1, v5 = b1, v6 = b2 - b1
 //     u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2 | u4 = h0, u5 = h0 + h1, u6 = h1
 //     3-tap: y0 = m0 + m1 + m2, y1 = m1 - m2 - m3 | 2-tap: y0 = m4 + m5, y1 = m5 + m6            (m_p = sum over channels of v_p u_p)
@@ -51,51 +51,6 @@ __global__ void wino_s2_u_kernel(const float* __restrict__ w, float* __restrict_
   for (int p = 0; p < 7; ++p) U[base + p * 512] = u[p];
 }
 
-#define GN_PK_ADD(o, x, y) asm volatile("v_pk_add_f32 %0, %1, %2" : "=&v"(o) : "v"(x), "v"(y))
-#define GN_PK_COPY(o, x) asm volatile("v_pk_mul_f32 %0, %1, 1.0 op_sel_hi:[1,0]" : "=&v"(o) : "v"(x))
-
-// the seven transformed fragments, one instruction each; NR raw rows d[0 .. NR-1]
-template <int KIND, int SB, int K, int NR>
-__device__ __forceinline__ void s2_piece(const f32x2 (&d)[NR], f32x2 (&v)[7]) {
-  constexpr int A0 = 0, A1 = KIND == 1 ? 2 : 1, A2 = KIND == 1 ? 4 : 2, A3 = KIND == 1 ? 6 : 3;
-  constexpr int B0 = KIND == 1 ? 1 : SB, B1 = KIND == 1 ? 3 : SB + 1, B2 = KIND == 1 ? 5 : SB + 2;
-  if constexpr (K == 0) GN_PK_SUB(v[0], d[A0], d[A2]);
-  else if constexpr (K == 1) GN_PK_ADD(v[1], d[A1], d[A2]);
-  else if constexpr (K == 2) GN_PK_SUB(v[2], d[A2], d[A1]);
-  else if constexpr (K == 3) GN_PK_SUB(v[3], d[A1], d[A3]);
-  else if constexpr (K == 4) GN_PK_SUB(v[4], d[B0], d[B1]);
-  else if constexpr (K == 5) GN_PK_COPY(v[5], d[B1]);
-  else GN_PK_SUB(v[6], d[B2], d[B1]);
-}
-template <int KIND, int SB, int NR, int K0, int K1>
-__device__ __forceinline__ void s2_run(const f32x2 (&d)[NR], f32x2 (&v)[7]) {
-  if constexpr (K0 < K1) {
-    s2_piece<KIND, SB, K0, NR>(d, v);
-    s2_run<KIND, SB, NR, K0 + 1, K1>(d, v);
-  }
-}
-template <int KIND, int SB, int NR, int K = 0>
-__device__ __forceinline__ void s2_bt_all(const f32x2 (&d)[NR], f32x2 (&v)[7]) {
-  if constexpr (K < 7) {
-    s2_piece<KIND, SB, K, NR>(d, v);
-    s2_bt_all<KIND, SB, NR, K + 1>(d, v);
-  }
-}
-
-__device__ __forceinline__ void s2_slot(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b) : "memory");
-}
-template <int O, int WAIT>
-__device__ __forceinline__ void s2_slot_rb(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b) {
-  asm volatile(
-      "ds_read_b128 %1, %5 offset:%6\n\t"
-      "ds_read_b128 %2, %5 offset:%7\n\t"
-      "s_waitcnt lgkmcnt(%8)\n\t"
-      "v_mfma_f32_16x16x4_f32 %0, %3, %4, %0"
-      : "+v"(c), "=&v"(nb0), "=&v"(nb1)
-      : "v"(a), "v"(b), "v"(addr_b), "i"(O), "i"(O + 1024), "i"(WAIT)
-      : "memory");
-}
 // slot 0: the next point's U values and the raw rows of the NEXT chunk; row j sits in plane j % NPL at plane row + j / NPL (PB = bytes per plane)
 template <int O, int PB>
 __device__ __forceinline__ void s2_slot_rba7(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b, f32x2 (&d)[7], unsigned addr_a) {
@@ -174,9 +129,9 @@ struct S2Chunk {
       } else if constexpr (I == 8) {
         if constexpr (NR == 7) s2_slot_rbw7<2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
         else s2_slot_rbw4<2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
-      } else if constexpr (I == 48) s2_slot_rb<0, 2>(acc[6][0], av, bv, bn[0], bn[1], addr_b_next);
-      else if constexpr (I % 8 == 0) s2_slot_rb<(P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
-      else s2_slot(acc[P][CT], av, bv);
+      } else if constexpr (I == 48) wino_slot_rb<0, 2>(acc[6][0], av, bv, bn[0], bn[1], addr_b_next);
+      else if constexpr (I % 8 == 0) wino_slot_rb<(P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
+      else wino_slot(acc[P][CT], av, bv);
       if constexpr ((I & 1) && (I >> 1) < NPIECES) dma(std::integral_constant<int, (I >> 1)>{});
       // the seven transform instructions in two runs (a vector instruction alone between two MFMAs of a wave costs 16 cycles, in a run 7: scripts/valu_rate.hip)
       if constexpr (I == 20) s2_run<KIND, SB, NR, 0, 4>(d, vn);
@@ -204,20 +159,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n16 = lane & 15, kq = lane >> 4;
-  const int bid = blockIdx.x;
-  int n_lin, slab;
-  if (patch >= 0 && bid < (int)(gridDim.x & ~511u)) {          // the XCD patch order of conv_pipe.hip
-    const int ps = patch & 255, pn = patch >> 8;
-    const int r = bid & 511, p = (bid >> 9) * 8 + (r & 7), idx = r >> 3;
-    slab = ((p >> ps) << (6 - pn)) + (idx >> pn);
-    n_lin = ((p & ((1 << ps) - 1)) << pn) + (idx & ((1 << pn) - 1));
-  } else {
-    n_lin = bid % n_tiles;
-    slab = bid / n_tiles;
-  }
-  const int n_tile = __builtin_amdgcn_readfirstlane(n_lin);
-  const int m_tile = __builtin_amdgcn_readfirstlane(slab % m_tiles);
-  const int b = __builtin_amdgcn_readfirstlane(slab / m_tiles);
+  const BlockTile bt = xcd_block_tile(patch, m_tiles, n_tiles);  // the XCD patch order of conv_epilogue.h
+  const int n_tile = bt.n_tile, m_tile = bt.m_tile, b = bt.b;
   const int t0 = m_tile * TT, n0 = n_tile * TN;
 
   f32x4 acc[NP][4];
@@ -294,7 +237,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
     const char* sb = reinterpret_cast<const char*>(smem);
 #pragma unroll
     for (int j = 0; j < NR; ++j) d[j] = *reinterpret_cast<const f32x2*>(sb + (base_a - lds0) + (j % TS) * RPER * 32 + (j / TS) * 32);
-    s2_bt_all<KIND, SB, NR>(d, V0);
+    s2_run<KIND, SB, NR, 0, 7>(d, V0);
     Bq[0][0] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0));
     Bq[0][1] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0) + 1024);
   }
@@ -402,12 +345,7 @@ static int launch_s2(const ConvArgs& a, const float* U, int off0, int offA, int 
     set_error("conv_wino_s2: bad grid %zu", blocks);
     return GN_EINVAL;
   }
-  int patch = -1;
-  {
-    const int pn = n_tiles % 8 == 0 ? 3 : (n_tiles == 4 ? 2 : -1);
-    const int ng = pn >= 0 ? n_tiles >> pn : 0;
-    if (pn >= 0 && ng <= 8 && (ng & (ng - 1)) == 0) patch = __builtin_ctz(ng) | (pn << 8);
-  }
+  const int patch = xcd_patch(n_tiles);             // (GN_CONV_NOPATCH is conv_pipe.hip's switch: these kernels always take the patch order)
   prof_begin(s);
   hipLaunchKernelGGL((conv_wino_s2_kernel<KIND, SB>), dim3((unsigned)blocks), dim3(256), lds, s, a, U, off0, m_tiles, n_tiles, patch, offA, offB);
   // flop = what the kernel EXECUTES: 7 multiplies per output pair and channel, 0.7 of the convolution's algorithmic count (kind 7)

@@ -19,9 +19,6 @@
 
 namespace gn {
 
-__device__ __forceinline__ void wg_slot(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b) : "memory");
-}
 // group slot 0: the next column tile's dy row pair (two tile pairs each)
 template <int O>
 __device__ __forceinline__ void wg_slot_e(f32x4& c, float a, float b, f32x2& e0, f32x2& e1, unsigned addr_b) {
@@ -63,11 +60,6 @@ __device__ __forceinline__ void wg_slot_e_wd(f32x4& c, float a, float b, f32x2& 
       : "v"(a), "v"(b), "v"(addr_b), "i"(O), "i"(O + 1), "i"(O + 4), "i"(O + 5)
       : "memory");
 }
-// group slot 4: the dy pair of the next column tile has to be there before its transform (WAIT = LDS operations issued after it that may stay in flight)
-template <int WAIT>
-__device__ __forceinline__ void wg_slot_w(f32x4& c, float a, float b, f32x2& e0, f32x2& e1) {
-  asm volatile("s_waitcnt lgkmcnt(%5)\n\tv_mfma_f32_16x16x4_f32 %0, %3, %4, %0" : "+v"(c), "+v"(e0), "+v"(e1) : "v"(a), "v"(b), "i"(WAIT) : "memory");
-}
 
 // One pair-step of a wave: 8 tiles (two k-steps), 48 MFMA slots ordered column tile (12 each) > k-step > point.  H = which half of the 16-tile chunk.
 // Beside the MFMAs: the dy pair of the NEXT column tile (read at group slot 0, transformed behind slots 5-8), the x pairs of the NEXT pair-step (read
@@ -85,7 +77,7 @@ struct WgPair {
       const float av = v[P][S], bv = dc[P][S];
       // where the next column tile's dy pair lives: this stage, next column tile; behind the last column tile the next pair-step's first one
       constexpr int OE = (CT < 3) ? (CT + 1) * 8 + 2 * H : (H == 0 ? 2 : 0);
-      if constexpr ((ABL & 8) != 0) wg_slot(acc[P][CT], av, bv);
+      if constexpr ((ABL & 8) != 0) wino_slot(acc[P][CT], av, bv);
       else if constexpr (I == 0) {
         if constexpr (H == 0) wg_slot_ea<OE, 2>(acc[P][CT], av, bv, dn[0], dn[5], addr_b, d, addr_a);                  // x pairs of this chunk's second half
         else wg_slot_ea<OE, 0>(acc[P][CT], av, bv, dn[0], dn[5], addr_b, d, addr_a_next);                               // ... of the next chunk's first half
@@ -93,8 +85,8 @@ struct WgPair {
       else if constexpr (G == 0) {
         if constexpr (CT == 3 && H == 1) wg_slot_e<OE>(acc[P][CT], av, bv, dn[0], dn[5], addr_b_next);
         else wg_slot_e<OE>(acc[P][CT], av, bv, dn[0], dn[5], addr_b);
-      } else if constexpr (G == 4) wg_slot_w<(I == 4 ? 6 : 0)>(acc[P][CT], av, bv, dn[0], dn[5]);
-      else wg_slot(acc[P][CT], av, bv);
+      } else if constexpr (G == 4) wino_slot_w<(I == 4 ? 6 : 0)>(acc[P][CT], av, bv, dn[0], dn[5]);     // group slot 4: the dy pair lands before its transform
+      else wino_slot(acc[P][CT], av, bv);
       if constexpr (G == 4) {
         constexpr int K = (H == 0 ? 0 : NP0) + CT;
         if constexpr (CT < (H == 0 ? NP0 : NP1)) dma(std::integral_constant<int, K>{});
@@ -212,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_wino_kernel(WgradArgs a, int off
         const float* pp = reinterpret_cast<const float*>(sb + (base_a[j >> 1] - lds0) + (j & 1) * 1280);
         d[j][0] = pp[0]; d[j][1] = pp[64];
       }
-      wino_bt_all(d, V0, tt, k15, km15);
+      wino_run<0, kWinoPieces>(d, V0, tt, k15, km15);
       const float* pb = reinterpret_cast<const float*>(sb + (base_b - lds0));
       D[0][0][0] = pb[0]; D[0][0][1] = pb[64]; D[0][5][0] = pb[256]; D[0][5][1] = pb[320];
       wino_a_piece<0>(D[0][0], D[0][5], D[0][1], D[0][2], D[0][3], D[0][4]); wino_a_piece<1>(D[0][0], D[0][5], D[0][1], D[0][2], D[0][3], D[0][4]);

@@ -1,7 +1,7 @@
-// Transform-domain weight gradient of the STRIDE-2 5-tap layers: the transposed form of conv_wino_s2.hip's F(2,3) + F(2,2),
+// Transform-domain weight gradient of the STRIDE-2 5-tap layers: the transposed form of conv_wino.hip's stride-2 F(2,3) + F(2,2),
 //
 //   Q_p[ci, co] = sum_{b, tau} V_p[b, tau, ci] * D_p[b, tau, co]      (seven points per output pair instead of ten taps)
-//   V = the forward kernel's input transform of the seven x rows 4 tau + off0 .. + 6:  a0 - a2, a1 + a2, a2 - a1, a1 - a3 | b0 - b1, b1, b2 - b1
+//   V = the forward kernel's input transform (wino_common.h: s2_piece, KIND 1) of the seven x rows 4 tau + off0 .. + 6:  a0 - a2, a1 + a2, a2 - a1, a1 - a3 | b0 - b1, b1, b2 - b1
 //   D = A^T of the dy pair (e0, e1) = (dy[2 tau], dy[2 tau + 1]):  e0, e0 + e1, e0 - e1, (-)e1 | e0, e0 + e1, e1   -- TWO packed additions; the operands repeat
 //   dW (reduce pass, fp64): w0 = Q0 + (Q1 + Q2) / 2, w2 = (Q1 - Q2) / 2, w4 = (Q1 + Q2) / 2 - Q3 | w1 = Q4 + Q5, w3 = Q5 + Q6      (Q3 carries +e1: sign here)
 //
@@ -16,9 +16,6 @@
 
 namespace gn {
 
-__device__ __forceinline__ void wg2_slot(f32x4& c, float a, float b) {
-  asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b) : "memory");
-}
 template <int O>
 __device__ __forceinline__ void wg2_slot_e(f32x4& c, float a, float b, f32x2& e0, f32x2& e1, unsigned addr_b) {
   asm volatile(
@@ -59,23 +56,6 @@ __device__ __forceinline__ void wg2_slot_e_wd(f32x4& c, float a, float b, f32x2&
       : "v"(a), "v"(b), "v"(addr_b), "i"(O), "i"(O + 1), "i"(O + 2), "i"(O + 3)
       : "memory");
 }
-template <int WAIT>
-__device__ __forceinline__ void wg2_slot_w(f32x4& c, float a, float b, f32x2& e0, f32x2& e1) {
-  asm volatile("s_waitcnt lgkmcnt(%5)\n\tv_mfma_f32_16x16x4_f32 %0, %3, %4, %0" : "+v"(c), "+v"(e0), "+v"(e1) : "v"(a), "v"(b), "i"(WAIT) : "memory");
-}
-
-#define GN_PK_ADD2(o, x, y) asm volatile("v_pk_add_f32 %0, %1, %2" : "=&v"(o) : "v"(x), "v"(y))
-#define GN_PK_COPY2(o, x) asm volatile("v_pk_mul_f32 %0, %1, 1.0 op_sel_hi:[1,0]" : "=&v"(o) : "v"(x))
-template <int K>
-__device__ __forceinline__ void wg2_x_piece(const f32x2 (&d)[7], f32x2 (&v)[7]) {
-  if constexpr (K == 0) GN_PK_SUB(v[0], d[0], d[4]);
-  else if constexpr (K == 1) GN_PK_ADD2(v[1], d[2], d[4]);
-  else if constexpr (K == 2) GN_PK_SUB(v[2], d[4], d[2]);
-  else if constexpr (K == 3) GN_PK_SUB(v[3], d[2], d[6]);
-  else if constexpr (K == 4) GN_PK_SUB(v[4], d[1], d[3]);
-  else if constexpr (K == 5) GN_PK_COPY2(v[5], d[3]);
-  else GN_PK_SUB(v[6], d[5], d[3]);
-}
 
 // One chunk (= one pair-step: 8 tiles, two k-steps) of a wave: 56 MFMA slots ordered column tile (14 each) > k-step > point.
 // D[buffer][0..3] = e0, e1, e0 + e1, e0 - e1 of a column tile; the B operand of point p is D[.][BI[p]].
@@ -95,17 +75,17 @@ struct Wg2Chunk {
       else if constexpr (G == 0) {
         if constexpr (CT == 3) wg2_slot_e<OE>(acc[P][CT], av, bv, dn[0], dn[1], addr_b_next);
         else wg2_slot_e<OE>(acc[P][CT], av, bv, dn[0], dn[1], addr_b);
-      } else if constexpr (G == 4) wg2_slot_w<(I == 4 ? 7 : 0)>(acc[P][CT], av, bv, dn[0], dn[1]);
-      else wg2_slot(acc[P][CT], av, bv);
+      } else if constexpr (G == 4) wino_slot_w<(I == 4 ? 7 : 0)>(acc[P][CT], av, bv, dn[0], dn[1]);
+      else wino_slot(acc[P][CT], av, bv);
       if constexpr (G == 4 && CT < NPIECES) dma(std::integral_constant<int, CT>{});
       // vector instructions in RUNS (alone between two MFMAs of a wave one costs 16 cycles, in a run 7: scripts/valu_rate.hip): the dy pair's two behind
       // slot 5 of every column tile, the next chunk's x transform as 4 + 3 behind slot 9 of column tiles 1 and 2
       if constexpr (G == 5) {
-        GN_PK_ADD2(dn[2], dn[0], dn[1]);
+        GN_PK_ADD(dn[2], dn[0], dn[1]);
         GN_PK_SUB(dn[3], dn[0], dn[1]);
       }
-      if constexpr (CT == 1 && G == 9) { wg2_x_piece<0>(d, vn); wg2_x_piece<1>(d, vn); wg2_x_piece<2>(d, vn); wg2_x_piece<3>(d, vn); }
-      if constexpr (CT == 2 && G == 9) { wg2_x_piece<4>(d, vn); wg2_x_piece<5>(d, vn); wg2_x_piece<6>(d, vn); }
+      if constexpr (CT == 1 && G == 9) s2_run<1, 0, 7, 0, 4>(d, vn);
+      if constexpr (CT == 2 && G == 9) s2_run<1, 0, 7, 4, 7>(d, vn);
       run<NPIECES, I + 1>(acc, v, vn, d, D, addr_b, addr_b_next, addr_a_next, dma);
     }
   }
@@ -191,10 +171,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_wino_s2_kernel(WgradArgs a, int 
         const float* pp = reinterpret_cast<const float*>(sb + (base_a[j >> 2] - lds0) + (j & 3) * 768);
         d[j][0] = pp[0]; d[j][1] = pp[64];
       }
-      wg2_x_piece<0>(d, V0); wg2_x_piece<1>(d, V0); wg2_x_piece<2>(d, V0); wg2_x_piece<3>(d, V0); wg2_x_piece<4>(d, V0); wg2_x_piece<5>(d, V0); wg2_x_piece<6>(d, V0);
+      s2_run<1, 0, 7, 0, 7>(d, V0);
       const float* pb = reinterpret_cast<const float*>(sb + (base_b - lds0));
       D[0][0][0] = pb[0]; D[0][0][1] = pb[64]; D[0][1][0] = pb[128]; D[0][1][1] = pb[192];
-      GN_PK_ADD2(D[0][2], D[0][0], D[0][1]);
+      GN_PK_ADD(D[0][2], D[0][0], D[0][1]);
       GN_PK_SUB(D[0][3], D[0][0], D[0][1]);
     }
     int st = 0;
