@@ -76,6 +76,10 @@ _SIGS = {
     'gn_optim_sumsq': [vp, sz, vp, vp],
     'gn_optim_clip_factor': [vp, sz, f32, vp, vp],
     'gn_fill_normal_dyn': [vp, sz, f32, vp, u64, u64, vp],
+    'gn_gaussian_noise_fwd': [vp, vp, sz, f32, u64, u64, vp],
+    'gn_gaussian_dropout_apply': [vp, vp, sz, f32, u64, u64, vp],
+    'gn_alpha_dropout_fwd': [vp, vp, sz, f32, f32, f32, f32, u64, u64, vp],
+    'gn_alpha_dropout_bwd': [vp, vp, sz, f32, f32, u64, u64, vp],
     'gn_bn_finalize_zero_debias_dyn': [vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     'gn_prof_enable': [i32],
     'gn_prof_reset': [],

@@ -21,8 +21,8 @@ import torch
 
 from . import engine, ops
 from .engine import Adam, Input, Model, Sequential, StepGraph, capturing, device, device_rng, to_device
-from .layers import (Activation, BatchNormalization, Conv1D, Conv2D, Dense, Dropout, Flatten, LeakyReLU, MaxPooling2D, MyLayer, ReLU,
-                     Reshape, UpSampling1D)
+from .layers import (Activation, AlphaDropout, BatchNormalization, Conv1D, Conv2D, Dense, Dropout, Flatten, GaussianDropout, GaussianNoise,
+                     LeakyReLU, MaxPooling2D, MyLayer, ReLU, Reshape, UpSampling1D)
 
 
 class Config(object):
@@ -90,29 +90,42 @@ def signal_pe_model(n_pix=1024):
     return model
 
 
-def signal_discriminator_model(n_pix=1024, num_lays=2, batchnorm=False, maxpool=False):
+_D_DROPOUT = {'dropout': Dropout, 'gaussian': GaussianDropout, 'alpha': AlphaDropout}
+
+
+def signal_discriminator_model(n_pix=1024, num_lays=2, batchnorm=False, maxpool=False, input_noise=0.0, dropout='dropout'):
     """bbhMahoGANy.py:408-498.  Defaults = the active configuration (:424-426); num_lays 1..6, batchnorm and maxpool are the reference's edit-the-file
-    knobs, layer order as written there (layer 2 normalises AFTER its activation, :449-450; layers 3-6 before, :457-458)."""
+    knobs, layer order as written there (layer 2 normalises AFTER its activation, :449-450; layers 3-6 before, :457-458).
+    Two knobs against the discriminator overpowering the generator, not in the reference: input_noise > 0 puts GaussianNoise(input_noise)
+    (instance noise) in front of the first Conv2D; dropout = 'gaussian' / 'alpha' replaces every Dropout(0.4) by GaussianDropout(0.4) /
+    AlphaDropout(0.4)."""
     drate, alpha, padding, weights, filtsize, n_neuron_scale, momentum = 0.4, 0.2, 'same', 'glorot_uniform', (5, 5), 4, 0.99
     if not 1 <= num_lays <= 6:
         raise ValueError('num_lays %r (the reference writes out layers 1..6, bbhMahoGANy.py:436-490)' % (num_lays,))
+    if dropout not in _D_DROPOUT:
+        raise ValueError('dropout %r: one of %s' % (dropout, sorted(_D_DROPOUT)))
+    input_noise = float(input_noise)
     model = Sequential(name='signal_discriminator')
+    if input_noise > 0.0:
+        model.add(GaussianNoise(input_noise, input_shape=(n_pix, 2, 1)))
     for i, (filters, strides) in enumerate(((64 * n_neuron_scale, (2, 1)), (128 * n_neuron_scale, (2, 1)), (256, (1, 1)), (512, (1, 1)), (1024, (1, 1)),
                                             (1024, (1, 1)))[:num_lays]):
-        kw = {'input_shape': (n_pix, 2, 1)} if i == 0 else {}
+        kw = {'input_shape': (n_pix, 2, 1)} if i == 0 and input_noise <= 0.0 else {}
         model.add(Conv2D(filters, filtsize, kernel_initializer=weights, strides=strides, padding=padding, **kw))
         if batchnorm and i >= 2:
             model.add(BatchNormalization(momentum=momentum))
         model.add(LeakyReLU(alpha=alpha))
         if batchnorm and i == 1:
             model.add(BatchNormalization(momentum=momentum))
-        model.add(Dropout(drate))
+        model.add(_D_DROPOUT[dropout](drate))
         if maxpool:
             model.add(MaxPooling2D(pool_size=(2, 1)))
     model.add(Flatten())
     model.add(Dense(1))
     model.add(Activation('sigmoid'))
     model._config = ('signal_discriminator_model', n_pix, num_lays, batchnorm, maxpool)
+    if input_noise > 0.0 or dropout != 'dropout':
+        model._config += (input_noise, dropout)
     return model
 
 
@@ -184,7 +197,7 @@ def build_and_compile(noise_signal, n_pix, lr=9e-5, do_pe=True, data_parallel=No
     """bbhMahoGANy.py:1089-1119, in the reference's order (the order fixes which weights each compiled model trains):
     the combined model is compiled while the discriminator is frozen, the discriminator after it is unfrozen.
     chi_loss (:97, :1106-1109): the combined model trains on chisquare_Loss instead of binary cross-entropy; filtsize (:228): the generator's filter size; d_config (:424-426): the discriminator's
-    num_lays / batchnorm / maxpool.  optimizer: a zero-argument factory called once per compiled model (each Keras model owns its optimizer);
+    num_lays / batchnorm / maxpool, and input_noise / dropout (signal_discriminator_model).  optimizer: a zero-argument factory called once per compiled model (each Keras model owns its optimizer);
     None is the reference's Adam(lr=lr, beta_1=0.5)."""
     if optimizer is None:
         optimizer = lambda: Adam(lr=lr, beta_1=0.5)     # noqa: E731

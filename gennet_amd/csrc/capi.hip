@@ -604,6 +604,22 @@ int gn_fill_normal(float* out, size_t n, float mean, float sd, uint64_t seed, ui
   GN_REQUIRE(out, "fill_normal: null pointer");
   return fill_normal(out, n, mean, sd, seed, offset, (hipStream_t)stream);
 }
+int gn_gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE((x && y) || !n, "gaussian_noise_fwd: null pointer");
+  return gaussian_noise_fwd(x, y, n, stddev, seed, offset, (hipStream_t)stream);
+}
+int gn_gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE((x && y) || !n, "gaussian_dropout_apply: null pointer");
+  return gaussian_dropout_apply(x, y, n, sd, seed, offset, (hipStream_t)stream);
+}
+int gn_alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE(((x && y) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_fwd: bad arguments");
+  return alpha_dropout_fwd(x, y, n, rate, a, b, alpha_p, seed, offset, (hipStream_t)stream);
+}
+int gn_alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE(((dy && dx) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_bwd: bad arguments");
+  return alpha_dropout_bwd(dy, dx, n, rate, a, seed, offset, (hipStream_t)stream);
+}
 int gn_gather_rows(const float* src, const int64_t* idx, float* out, int rows, int width, void* stream) {
   GN_REQUIRE(src && idx && out && rows >= 0 && width > 0, "gather_rows: bad arguments");
   return gather_rows(src, idx, out, rows, width, (hipStream_t)stream);

@@ -194,6 +194,11 @@ int gather_rows(const float* src, const int64_t* idx, float* out, int rows, int 
 int axpy(float* y, const float* x, float a, size_t n, hipStream_t s);
 int fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, hipStream_t s);
 int fill_normal(float* out, size_t n, float mean, float sd, uint64_t seed, uint64_t offset, hipStream_t s, const float* sd_dev = nullptr);
+// noise_layers.hip
+int gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, hipStream_t s);
+int gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, hipStream_t s);
+int alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, hipStream_t s);
+int alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, hipStream_t s);
 size_t colred_workspace_bytes(size_t rows, int C);
 int colred_run(int mode, ColRedArgs a, void* ws, size_t ws_bytes, double* out_f64, float* out_f32, hipStream_t s);
 int colred_finalize(const double* part, double* out_f64, size_t n, int chunks, hipStream_t s);   // out[i] = sum_k part[k*n + i], fixed order

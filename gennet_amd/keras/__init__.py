@@ -6,6 +6,7 @@
     from gennet_amd.keras.layers.normalization import BatchNormalization
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
+    from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -44,9 +45,10 @@ _norm = _pick(_layers, 'BatchNormalization')
 _conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'UpSampling1D', 'MaxPooling2D'),
              **_unused('37-38', 'UpSampling2D', 'Conv2DTranspose', 'AveragePooling1D', 'MaxPooling1D'))
 _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU'), **_unused('39', 'ThresholdedReLU'))
+_noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
-_top.update(_unused('33-34', 'GlobalAveragePooling1D', 'AlphaDropout', 'GaussianDropout', 'GaussianNoise'))
-for _d in (_core, _norm, _conv, _act):
+_top.update(_unused('33-34', 'GlobalAveragePooling1D'))
+for _d in (_core, _norm, _conv, _act, _noise):
     _top.update((k, v) for k, v in _d.items() if k in _layers.__dict__)
 
 _TREE = {
@@ -59,6 +61,7 @@ _TREE = {
     'layers.normalization': _norm,
     'layers.convolutional': _conv,
     'layers.advanced_activations': _act,
+    'layers.noise': _noise,
 }
 
 

@@ -201,6 +201,10 @@ def layer_config(layer):
         cfg.update(activation=_ACT_OF_SPEC[layer.act_spec[0]])
     elif isinstance(layer, L.Dropout):
         cfg.update(rate=layer.rate, noise_shape=None, seed=None)
+    elif isinstance(layer, L.GaussianNoise):
+        cfg.update(stddev=layer.stddev)
+    elif isinstance(layer, (L.GaussianDropout, L.AlphaDropout)):
+        cfg.update(rate=layer.rate)
     elif isinstance(layer, L.Reshape):
         cfg.update(target_shape=list(getattr(layer, 'target_shape_arg', layer.target_shape)))
     elif isinstance(layer, L.Flatten):
@@ -289,6 +293,12 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.Activation(cfg['activation'], **kw)
     if class_name == 'Dropout':
         return L.Dropout(cfg['rate'], **kw)
+    if class_name == 'GaussianNoise':
+        return L.GaussianNoise(cfg['stddev'], **kw)
+    if class_name == 'GaussianDropout':
+        return L.GaussianDropout(cfg['rate'], **kw)
+    if class_name == 'AlphaDropout':
+        return L.AlphaDropout(cfg['rate'], noise_shape=cfg.get('noise_shape'), seed=cfg.get('seed'), **kw)
     if class_name == 'Reshape':
         return L.Reshape(tuple(cfg['target_shape']), **kw)
     if class_name == 'Flatten':

@@ -529,6 +529,126 @@ class Dropout(Layer):
         return ops.dropout_apply(dy.contiguous(), mask, self.rate)
 
 
+_SELU_ALPHA_P = -1.6732632423543772848170429916717 * 1.0507009873554804934193349852946     # keras' AlphaDropout: -alpha * scale of SELU
+
+
+def _noise_rate(layer_name, rate):
+    rate = float(rate)
+    if rate != rate:
+        raise ValueError('%s(rate=nan)' % layer_name)
+    return rate
+
+
+class _NoiseLayer(Layer):
+    """Keras 2.2.4 layers/noise.py: a training-phase-only layer whose draw is made inside its own kernel (gennet_amd/csrc/noise_layers.hip).
+    The forward takes ceil(n / 4) counters of the device stream (under ctx.row_map, those of its global rows, one launch per block, as
+    Dropout.make_mask); the tape keeps only (seed, [(local row start, rows, counter offset)]) and the backward regenerates the draw from it.
+    Not a Dropout for the planner: drop_rate stays None, so no conv / BatchNormalization epilogue absorbs it."""
+
+    def _active(self):
+        return True
+
+    def _run(self, kind, x, seed, offset, out):
+        raise NotImplementedError
+
+    def _draws(self, ctx, shape):
+        n = int(np.prod(shape))
+        if ctx.row_map is None:
+            seed, off = device_rng().take(n)
+            return seed, [(0, shape[0], off)]
+        blocks, grows = ctx.row_map
+        if sum(nr for _, nr in blocks) != shape[0]:
+            raise ValueError('%s: the row map covers %d rows, the tensor has %d' % (self.name, sum(nr for _, nr in blocks), shape[0]))
+        seed, offs = device_rng().take_rows(n // shape[0], blocks, grows)
+        parts, r0 = [], 0
+        for (_, nr), off in zip(blocks, offs):
+            parts.append((r0, nr, off))
+            r0 += nr
+        return seed, parts
+
+    def _apply(self, kind, x, seed, parts):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        for r0, nr, off in parts:
+            self._run(kind, x[r0:r0 + nr], seed, off, y[r0:r0 + nr])
+        return y
+
+    def forward(self, ctx, node, x):
+        if not ctx.training or not self._active():
+            ctx.tape[node.index] = None
+            return x
+        seed, parts = self._draws(ctx, x.shape)
+        ctx.tape[node.index] = (seed, parts)
+        return self._apply('fwd', x, seed, parts)
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        t = ctx.tape.pop(node.index)
+        if t is None:
+            return dy
+        return self._apply('bwd', dy, t[0], t[1])
+
+
+class GaussianNoise(_NoiseLayer):
+    """keras.layers.GaussianNoise(stddev): y = x + stddev * z in the training phase (the reference's sibling models put GaussianNoise(1) on the
+    discriminator's input).  The gradient is the identity."""
+
+    def __init__(self, stddev, **kw):
+        Layer.__init__(self, **kw)
+        self.stddev = float(stddev)
+        if not (self.stddev >= 0.0 and np.isfinite(self.stddev)):
+            raise ValueError('GaussianNoise(stddev=%r): a finite standard deviation >= 0' % (stddev,))
+
+    def _run(self, kind, x, seed, offset, out):
+        ops.gaussian_noise(x, self.stddev, seed, offset, out)
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        ctx.tape.pop(node.index)
+        return dy
+
+
+class GaussianDropout(_NoiseLayer):
+    """keras.layers.GaussianDropout(rate): y = x * m, m ~ N(1, rate / (1 - rate)) in the training phase; dx = dy * m (the same pass with the
+    forward's counters).  rate outside (0, 1) is the identity, as in keras."""
+
+    def __init__(self, rate, **kw):
+        Layer.__init__(self, **kw)
+        self.rate = _noise_rate('GaussianDropout', rate)
+        self.sd = float(np.float32(np.sqrt(self.rate / (1.0 - self.rate)))) if self._active() else 0.0
+
+    def _active(self):
+        return 0.0 < self.rate < 1.0
+
+    def _run(self, kind, x, seed, offset, out):
+        ops.gaussian_dropout(x, self.sd, seed, offset, out)
+
+
+class AlphaDropout(_NoiseLayer):
+    """keras.layers.AlphaDropout(rate): a dropped value becomes SELU's negative saturation alpha_p, then the affine map a * x + b that keeps
+    zero mean and unit variance; in the training phase only.  rate outside (0, 1) is the identity, as in keras.  Every draw comes from the
+    process's one device stream, so noise_shape and seed are refused rather than ignored."""
+
+    def __init__(self, rate, noise_shape=None, seed=None, **kw):
+        Layer.__init__(self, **kw)
+        if noise_shape is not None:
+            raise NotImplementedError('AlphaDropout(noise_shape=%r): only the full-shape draw is implemented' % (noise_shape,))
+        if seed is not None:
+            raise NotImplementedError('AlphaDropout(seed=%r): the draws come from the device stream (engine.set_device_seed)' % (seed,))
+        self.rate = _noise_rate('AlphaDropout', rate)
+        if self._active():
+            r, ap = self.rate, _SELU_ALPHA_P
+            a = ((1.0 - r) * (1.0 + r * ap ** 2)) ** -0.5
+            self.a, self.b, self.alpha_p = float(np.float32(a)), float(np.float32(-a * ap * r)), float(np.float32(ap))
+
+    def _active(self):
+        return 0.0 < self.rate < 1.0
+
+    def _run(self, kind, x, seed, offset, out):
+        if kind == 'fwd':
+            ops.alpha_dropout_fwd(x, self.rate, self.a, self.b, self.alpha_p, seed, offset, out)
+        else:
+            ops.alpha_dropout_bwd(x, self.rate, self.a, seed, offset, out)
+
+
 class Reshape(Layer):
     shape_only = True
 

@@ -516,6 +516,39 @@ def fill_normal(shape, mean, std, seed, offset, device):
     return t
 
 
+def _noise_out(x, out):
+    _chk(x, out)
+    return torch.empty_like(x) if out is None else out
+
+
+def gaussian_noise(x, stddev, seed, offset, out=None):
+    """y = x + stddev * z, z = fill_normal's N(0, 1) draw at (seed, offset) (GaussianNoise)."""
+    y = _noise_out(x, out)
+    _lib.call('gn_gaussian_noise_fwd', _p(x), _p(y), x.numel(), float(stddev), int(seed), int(offset), _stream())
+    return y
+
+
+def gaussian_dropout(x, sd, seed, offset, out=None):
+    """y = x * (1 + sd * z) (GaussianDropout's forward, and its backward with the forward's (seed, offset))."""
+    y = _noise_out(x, out)
+    _lib.call('gn_gaussian_dropout_apply', _p(x), _p(y), x.numel(), float(sd), int(seed), int(offset), _stream())
+    return y
+
+
+def alpha_dropout_fwd(x, rate, a, b, alpha_p, seed, offset, out=None):
+    """y = keep ? a * x + b : a * alpha_p + b, keep = dropout_mask's draw at (seed, offset) (AlphaDropout)."""
+    y = _noise_out(x, out)
+    _lib.call('gn_alpha_dropout_fwd', _p(x), _p(y), x.numel(), float(rate), float(a), float(b), float(alpha_p), int(seed), int(offset), _stream())
+    return y
+
+
+def alpha_dropout_bwd(dy, rate, a, seed, offset, out=None):
+    """dx = keep ? a * dy : 0 with the forward's (seed, offset)."""
+    dx = _noise_out(dy, out)
+    _lib.call('gn_alpha_dropout_bwd', _p(dy), _p(dx), dy.numel(), float(rate), float(a), int(seed), int(offset), _stream())
+    return dx
+
+
 def gather_rows(src, idx):
     _chk(src, idx)
     rows, width = idx.numel(), src.shape[1]

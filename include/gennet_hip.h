@@ -196,6 +196,17 @@ int gn_assemble_d_batch(const float* real, const float* noise, const float* fake
 /* uniform(lo,hi) and normal(mean,std) fills from Philox (host RNG replacement for bbhMahoGANy.py:1161,1247,1277,1295) */
 int gn_fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, void* stream);
 int gn_fill_normal(float* out, size_t n, float mean, float std, uint64_t seed, uint64_t offset, void* stream);
+/* Keras 2.2.4 noise layers (layers/noise.py), one pass each with the draw made in the same pass: element i uses Philox4x32-10 counter
+ * (offset + i/4), lane i%4.  z is gn_fill_normal's N(0,1) draw bit for bit (gn_gaussian_noise_fwd at x = 0 equals gn_fill_normal(mean 0, std
+ * stddev); gn_gaussian_dropout_apply at x = 1 equals gn_fill_normal(mean 1, std sd)); keep is gn_dropout_mask's test (u >= rate).
+ *   GaussianNoise:   y = x + stddev z
+ *   GaussianDropout: y = x (1 + sd z), sd = sqrt(rate / (1 - rate)); also the backward (dx = dy (1 + sd z)) with the forward's (seed, offset)
+ *   AlphaDropout:    y = keep ? a x + b : a alpha_p + b;   backward dx = keep ? a dy : 0 with the forward's (seed, offset); 0 < rate < 1
+ * x == y (in place) is allowed. */
+int gn_gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, void* stream);
+int gn_gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, void* stream);
+int gn_alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, void* stream);
+int gn_alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, void* stream);
 /* out[i,:] = src[idx[i],:] (random.sample batch gather, bbhMahoGANy.py:1156-1157, :1244) */
 int gn_gather_rows(const float* src, const int64_t* idx, float* out, int rows, int width, void* stream);
 /* y[i] += a * x[i] */
@@ -300,7 +311,7 @@ int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, f
  * replayed.  Scalars that change from step to step would be frozen into the graph as by-value kernel arguments; these entry points read them
  * from device memory instead (the host refreshes one small block before each replay).
  * gn_set_rng_base: from now on (this host thread) every Philox kernel of the library -- gn_dropout_mask, gn_fill_uniform, gn_fill_normal(_dyn),
- * gn_bn_apply_dropgen -- adds *base_dev to its counter offset at run time; NULL switches it off.  With base = (stream position at replay) -
+ * gn_bn_apply_dropgen, gn_gaussian_noise_fwd, gn_gaussian_dropout_apply, gn_alpha_dropout_fwd, gn_alpha_dropout_bwd -- adds *base_dev to its counter offset at run time; NULL switches it off.  With base = (stream position at replay) -
  * (stream position at capture) a replay draws exactly what the un-captured step would have drawn. */
 int gn_set_rng_base(const uint64_t* base_dev);
 /* gn_adam_step with lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) read from device memory */

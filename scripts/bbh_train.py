@@ -48,6 +48,10 @@ def main():
     ap.add_argument('--decay', type=float, default=0.0, help="Keras' decay: lr / (1 + decay * iterations)")
     ap.add_argument('--clipnorm', type=float, default=0.0, help="Keras' clipnorm over all trained weights of each compiled model (0: off)")
     ap.add_argument('--clipvalue', type=float, default=0.0, help="Keras' clipvalue, after clipnorm (0: off)")
+    ap.add_argument('--d-input-noise', type=float, default=0.0,
+                    help='standard deviation of GaussianNoise (instance noise) on the discriminator input, training phase only (0: none, as the reference)')
+    ap.add_argument('--d-dropout', default='dropout', choices=('dropout', 'gaussian', 'alpha'),
+                    help="the discriminator's Dropout(0.4) layers as Dropout (the reference), GaussianDropout or AlphaDropout at the same rate")
     ap.add_argument('--old-model', action='store_true', help='do_old_model (:1133-1138): start all four networks from the files of an earlier run in --out')
     ap.add_argument('--only-old-pe-model', action='store_true', help='do_only_old_pe_model (:1141-1142): load best_models/signal_pe.h5 and skip the CNN loop')
     ap.add_argument('--sanity-check', default=None,
@@ -70,7 +74,9 @@ def main():
         noise_signal = np.reshape(pickle.load(f, encoding='latin1') * args.event_scale, (args.n_pix, 1))
 
     opt = bbh.optimizer_factory(args.optimizer, args.lr, args.decay, args.clipnorm or None, args.clipvalue or None)
-    nets = bbh.build_and_compile(noise_signal, args.n_pix, lr=args.lr, data_parallel=dp, chi_loss=args.chi_loss, n_sig=args.n_sig, optimizer=opt)
+    d_config = {'input_noise': args.d_input_noise, 'dropout': args.d_dropout}
+    nets = bbh.build_and_compile(noise_signal, args.n_pix, lr=args.lr, data_parallel=dp, chi_loss=args.chi_loss, n_sig=args.n_sig, optimizer=opt,
+                                 d_config=d_config)
     if dp:
         for m in (nets.generator, nets.signal_discriminator, nets.signal_pe):
             dp.sync_model(m)
