@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_family as CF
 from oracle import keras_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -52,33 +53,59 @@ def test_predict_ragged_and_short_batches():
     assert none[0].shape == (0, 1) and none[1].shape == (0, 1)
 
 
-def test_smallest_shapes_of_each_conv_family():
-    from gennet_amd import ops
-    rng = np.random.RandomState(3)
-    for (B, L, Cin, Cout, k, s, padding) in ((1, 5, 16, 8, 5, 1, 'valid'),         # one output row, MFMA path, Cout below one tile
-                                             (1, 1, 1, 4, 1, 1, 'valid'),          # small-Cin, a single sample
-                                             (1, 5, 8, 1, 5, 1, 'same'),           # small-Cout
-                                             (1, 2, 16, 16, 5, 2, 'same')):        # stride 2 on two rows: every tap but one is padding
+_FWD_ORACLE = CF.OneCase()
+
+SMALLEST_SHAPES = (
+    # B, L, Cin, Cout, k, stride, padding; forward family under 'fp32', under 'wino'
+    (1, 5, 16, 8, 5, 1, 'valid',   'direct', 'direct'),     # one output row, MFMA path, Cout below one tile
+    (1, 1, 1, 4, 1, 1, 'valid',    'small', 'small'),       # small-Cin, a single sample
+    (1, 5, 8, 1, 5, 1, 'same',     'small', 'small'),       # small-Cout
+    (1, 2, 16, 16, 5, 2, 'same',   'direct', 'direct'),     # stride 2 on two rows: every tap but one is padding
+)
+SMALL_CIN_STRIDES = (
+    (2, 4001, 4, 16, 5, 3, 'same',  'small', 'small'),
+    (1, 5000, 1, 64, 5, 9, 'valid', 'small', 'small'),
+    (2, 3000, 3, 8, 5, 5, 'same',   'small', 'small'),
+)
+
+
+def _forward_oracle(seed, cases):
+    rng = np.random.RandomState(seed)
+    out = []
+    for (B, L, Cin, Cout, k, s, padding) in (c[:7] for c in cases):
         x = rng.randn(B, L, Cin).astype(np.float32); w = rng.randn(k, Cin, Cout).astype(np.float32); b = rng.randn(Cout).astype(np.float32)
+        out.append((x, w, b, K.conv1d_fwd(x.astype(np.float64), w.astype(np.float64), b.astype(np.float64), s, padding)))
+    return out
+
+
+def _forward_cases(math, seed, cases):
+    """Each case's forward against the oracle (computed once for both maths) under `math`, asserted to reach the family its row names."""
+    from gennet_amd import ops
+    for (B, L, Cin, Cout, k, s, padding, fam_fp32, fam_wino), (x, w, b, ref) in zip(cases, _FWD_ORACLE.get(seed, lambda: _forward_oracle(seed, cases))):
         Lout, pl = ops.conv_geometry(L, k, s, padding)
-        ref = K.conv1d_fwd(x.astype(np.float64), w.astype(np.float64), b.astype(np.float64), s, padding)
-        y = ops.conv1d_fwd(torch.tensor(x).to(dev()), torch.tensor(w).to(dev()), torch.tensor(b).to(dev()), s, pl, Lout).cpu().numpy()
+        xd, wd, bd = torch.tensor(x).to(dev()), torch.tensor(w).to(dev()), torch.tensor(b).to(dev())
+        with ops.conv_math(math):
+            y = CF.run('fwd', fam_fp32 if math == 'fp32' else fam_wino, lambda: ops.conv1d_fwd(xd, wd, bd, s, pl, Lout)).cpu().numpy()
         assert y.shape == ref.shape
         assert np.abs(y - ref).max() <= 2e-5 * max(np.abs(ref).max(), 1.0)
+
+
+def test_smallest_shapes_of_each_conv_family():
+    _forward_cases('fp32', 3, SMALLEST_SHAPES)
+
+
+def test_smallest_shapes_of_each_conv_family_under_wino():
+    _forward_cases('wino', 3, SMALLEST_SHAPES)
 
 
 def test_small_cin_conv_strides_beyond_two():
     """The small-Cin kernel stages its input window in a fixed LDS array: strides > 2 get fewer rows per block instead of writing
     past it (Conv1D(16,5,strides=3) on 4 channels and Conv1D(64,5,strides=9) on 1 channel: the shapes ADVICE round 1 named)."""
-    from gennet_amd import ops
-    rng = np.random.RandomState(4)
-    for (B, L, Cin, Cout, k, s, padding) in ((2, 4001, 4, 16, 5, 3, 'same'), (1, 5000, 1, 64, 5, 9, 'valid'), (2, 3000, 3, 8, 5, 5, 'same')):
-        x = rng.randn(B, L, Cin).astype(np.float32); w = rng.randn(k, Cin, Cout).astype(np.float32); b = rng.randn(Cout).astype(np.float32)
-        Lout, pl = ops.conv_geometry(L, k, s, padding)
-        ref = K.conv1d_fwd(x.astype(np.float64), w.astype(np.float64), b.astype(np.float64), s, padding)
-        y = ops.conv1d_fwd(torch.tensor(x).to(dev()), torch.tensor(w).to(dev()), torch.tensor(b).to(dev()), s, pl, Lout).cpu().numpy()
-        assert y.shape == ref.shape
-        assert np.abs(y - ref).max() <= 2e-5 * max(np.abs(ref).max(), 1.0)
+    _forward_cases('fp32', 4, SMALL_CIN_STRIDES)
+
+
+def test_small_cin_conv_strides_beyond_two_under_wino():
+    _forward_cases('wino', 4, SMALL_CIN_STRIDES)
 
 
 def test_indexing_beyond_2_to_31_elements():

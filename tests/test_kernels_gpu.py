@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_family as CF
 from oracle import keras_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -41,76 +42,125 @@ def f32(a):
 
 
 CONV_CASES = [
-    # B, L, Cin, Cout, k, stride, padding
-    (2, 64, 16, 128, 5, 1, 'same'),       # one tile, exact channels
-    (3, 133, 64, 128, 5, 1, 'valid'),     # ragged M tile
-    (2, 150, 64, 128, 5, 2, 'valid'),     # stride 2 (de-interleaved slab)
-    (2, 77, 32, 64, 5, 2, 'same'),        # narrow-N tile config
-    (1, 300, 48, 192, 5, 1, 'same'),      # Cout not a multiple of the N tile, Cin = 3 chunks
-    (2, 40, 20, 72, 5, 2, 'same'),        # Cin not a multiple of KC
-    (2, 96, 1, 64, 5, 2, 'same'),         # small-Cin (point-estimator first layer)
-    (2, 96, 1, 64, 5, 1, 'same'),
-    (3, 50, 2, 512, 5, 2, 'same'),        # folded discriminator first layer
-    (2, 64, 256, 1, 5, 1, 'same'),        # small-Cout (generator output conv)
-    (2, 64, 128, 2, 5, 2, 'same'),
-    (3, 70, 512, 1, 5, 1, 'valid'),       # Cout = 1 row-run kernel, ragged run, two channel passes
-    (2, 61, 128, 3, 5, 1, 'same'),        # small-Cout weight gradient looped over input rows
-    (2, 50, 16, 64, 3, 1, 'same'),        # 3 taps (the folded UpSampling1D -> Conv1D layers), matrix-core weight gradient
-    (2, 45, 64, 128, 2, 1, 'valid'),      # 2 taps
-    (3, 66, 32, 64, 4, 2, 'same'),        # 4 taps, stride 2
-    (9, 2100, 16, 512, 5, 1, 'same'),     # 648 blocks of the tall tile: 512 in XCD patch order (8 slabs x 8 column tiles) + a plain-order tail
-    (20, 1100, 16, 512, 3, 1, 'same'),    # 720 blocks of the square tile, 4 column tiles: 16 x 4 patches + tail
+    # B, L, Cin, Cout, k, stride, padding; the family each direction reaches (fwd dgrad wgrad, csrc/capi.hip select_conv) under 'fp32' and under 'wino'
+    (2, 64, 16, 128, 5, 1, 'same',      'direct direct direct', 'direct direct direct'),       # one tile, exact channels
+    (3, 133, 64, 128, 5, 1, 'valid',    'direct direct direct', 'wino wino wino'),             # ragged M tile
+    (2, 150, 64, 128, 5, 2, 'valid',    'direct merged direct', 'wino_s2 wino_s2 wino_s2'),    # stride 2 (de-interleaved slab)
+    (2, 77, 32, 64, 5, 2, 'same',       'direct phases direct', 'wino_s2 phases direct'),      # narrow-N tile config
+    (1, 300, 48, 192, 5, 1, 'same',     'direct direct direct', 'wino direct direct'),         # Cout not a multiple of the N tile, Cin = 3 chunks
+    (2, 40, 20, 72, 5, 2, 'same',       'direct phases direct', 'direct phases direct'),       # Cin not a multiple of KC
+    (2, 96, 1, 64, 5, 2, 'same',        'small small small', 'small small small'),             # small-Cin (point-estimator first layer)
+    (2, 96, 1, 64, 5, 1, 'same',        'small small small', 'small small small'),
+    (3, 50, 2, 512, 5, 2, 'same',       'small small small', 'small small small'),             # folded discriminator first layer
+    (2, 64, 256, 1, 5, 1, 'same',       'small small small', 'small small small'),             # small-Cout (generator output conv)
+    (2, 64, 128, 2, 5, 2, 'same',       'small small small', 'small small small'),
+    (3, 70, 512, 1, 5, 1, 'valid',      'small small small', 'small small small'),             # Cout = 1 row-run kernel, ragged run, two channel passes
+    (2, 61, 128, 3, 5, 1, 'same',       'small small small', 'small small small'),             # small-Cout weight gradient looped over input rows
+    (2, 50, 16, 64, 3, 1, 'same',       'direct direct direct', 'direct direct direct'),       # 3 taps (the folded UpSampling1D -> Conv1D layers), matrix-core weight gradient
+    (2, 45, 64, 128, 2, 1, 'valid',     'direct direct direct', 'direct direct direct'),       # 2 taps
+    (3, 66, 32, 64, 4, 2, 'same',       'direct phases direct', 'direct phases direct'),       # 4 taps, stride 2
+    (9, 2100, 16, 512, 5, 1, 'same',    'direct direct direct', 'direct direct direct'),       # 648 blocks of the tall tile: 512 in XCD patch order (8 slabs x 8 column tiles) + a plain-order tail
+    (20, 1100, 16, 512, 3, 1, 'same',   'direct direct direct', 'direct direct direct'),       # 720 blocks of the square tile, 4 column tiles: 16 x 4 patches + tail
     # round 3: the narrow-wave forms for launches with fewer than two wave tiles per SIMD (conv_pipe_try), every block height
-    (8, 512, 16, 1024, 5, 1, 'same'),     # forward: 256 blocks of 8 narrow waves (256 x 64); data gradient (Cout 16) on the plain path
-    (8, 250, 16, 1024, 5, 1, 'same'),     # forward: 128 x 64 blocks of 4 narrow waves, ragged rows (250 = 128 + 122)
-    (8, 1000, 16, 512, 5, 2, 'valid'),    # stride-2 forward on narrow waves (M = 498)
-    (8, 513, 1024, 16, 5, 2, 'same'),     # data gradient merged over both phases, odd length (257 output pairs, the last without its odd row),
-                                          # 256-row blocks of 8 narrow waves with two accumulator sets; 'same' padding: even taps -> odd rows
-    (7, 700, 1024, 16, 5, 2, 'valid'),    # ... 128-row blocks, 'valid' padding: even taps -> even rows
-    (2, 131, 128, 24, 5, 2, 'same'),      # ... 64-row blocks, ragged rows
-    (3, 700, 64, 128, 5, 1, 'same'),      # weight gradient K-splits INSIDE batch elements (14 ranges of 5 chunks over 3 x 22 chunks, ragged last chunk)
-    (5, 333, 64, 64, 5, 2, 'valid'),      # ... stride 2
+    (8, 512, 16, 1024, 5, 1, 'same',    'direct direct direct', 'direct direct direct'),       # forward: 256 blocks of 8 narrow waves (256 x 64); data gradient (Cout 16) on the plain path
+    (8, 250, 16, 1024, 5, 1, 'same',    'direct direct direct', 'direct direct direct'),       # forward: 128 x 64 blocks of 4 narrow waves, ragged rows (250 = 128 + 122)
+    (8, 1000, 16, 512, 5, 2, 'valid',   'direct phases direct', 'direct phases direct'),       # stride-2 forward on narrow waves (M = 498)
+    (8, 513, 1024, 16, 5, 2, 'same',    'direct merged direct', 'direct merged direct'),       # data gradient merged over both phases, odd length (257 output pairs, the last
+                                                                                               # without its odd row), 256-row blocks of 8 narrow waves with two accumulator sets;
+                                                                                               # 'same' padding: even taps -> odd rows
+    (7, 700, 1024, 16, 5, 2, 'valid',   'direct merged direct', 'direct merged direct'),       # ... 128-row blocks, 'valid' padding: even taps -> even rows
+    (2, 131, 128, 24, 5, 2, 'same',     'direct merged direct', 'direct merged direct'),       # ... 64-row blocks, ragged rows
+    (3, 700, 64, 128, 5, 1, 'same',     'direct direct direct', 'wino wino wino'),             # weight gradient K-splits INSIDE batch elements (direct: 14 ranges of 5 chunks
+                                                                                               # over 3 x 22 chunks, ragged last chunk)
+    (5, 333, 64, 64, 5, 2, 'valid',     'direct merged direct', 'wino_s2 wino_s2 wino_s2'),    # ... stride 2
+    # small-channel members (csrc/small_conv.hip) in all three directions
+    (2, 77, 64, 1, 5, 1, 'same',        'small small small', 'small small small'),             # Cout = 1 below Cin 256: conv_smallcout_kernel<1>, not the row-run kernel
+    (2, 77, 128, 1, 5, 2, 'valid',      'small small small', 'small small small'),             # ... stride 2: strided Cout = 1 forward, small-Cin data-gradient phases
+    (2, 50, 64, 4, 5, 2, 'same',        'small small small', 'small small small'),             # Cout = 4 outside the tap fold, stride 2
+    (3, 257, 3, 64, 5, 1, 'same',       'small small small', 'small small small'),             # Cin = 3: smallcin<3> forward, smallcout<3> data gradient, tabled weight gradient
+    (2, 129, 4, 128, 5, 2, 'valid',     'small small small', 'small small small'),             # Cin = 4, stride 2, ragged
+    (2, 100, 2, 64, 3, 1, 'same',       'small small small', 'small small small'),             # small channels with 3 taps
+    (2, 100, 64, 2, 1, 1, 'valid',      'small small small', 'small small small'),             # ... with 1 tap
+    (5, 131, 64, 2, 5, 1, 'same',       'small small small', 'small small small'),             # weight-gradient row chunks spanning batch boundaries
+    (16, 2048, 1, 64, 5, 2, 'same',     'small small small', 'small small small'),             # 128 weight-gradient chunks: the two-level sum_partials reduce
+    # each rule of the selector just inside and just outside its gate
+    (2, 70, 32, 64, 5, 1, 'same',       'direct direct direct', 'wino direct direct'),         # transform-domain forward from Cin 32 ...
+    (2, 70, 24, 64, 5, 1, 'same',       'direct direct direct', 'direct direct direct'),       # ... not at Cin 24
+    (2, 70, 64, 64, 5, 1, 'same',       'direct direct direct', 'wino wino wino'),             # Cout % 64 == 0 ...
+    (2, 70, 64, 96, 5, 1, 'same',       'direct direct direct', 'direct wino direct'),         # ... Cout 96: forward and weight gradient direct, the data gradient (Cout' = Cin 64) wino
+    (2, 70, 64, 128, 5, 1, 'valid',     'direct direct direct', 'wino wino wino'),             # transform-domain weight gradient at Cin % 64 == 0 ...
+    (2, 70, 72, 128, 5, 1, 'valid',     'direct direct direct', 'wino direct direct'),         # ... not at Cin 72 (the forward still is)
+    (2, 90, 64, 32, 5, 2, 'same',       'direct merged direct', 'direct wino_s2 direct'),      # stride-2 data gradient on wino_s2 from the layer's Cout 32 ...
+    (2, 90, 64, 24, 5, 2, 'same',       'direct merged direct', 'direct merged direct'),       # ... merged at Cout 24
+    (8, 896, 1024, 16, 5, 2, 'same',    'direct merged direct', 'direct merged direct'),       # merged data gradient at 8 x 7 x 16 x 2 = 1792 wave tiles (merge_below 2048) ...
+    (8, 898, 1024, 16, 5, 2, 'same',    'direct phases direct', 'direct phases direct'),       # ... two phase launches at 8 x 8 x 16 x 2 = 2048
+]
+
+_CONV_ORACLE = CF.OneCase()
+
+
+def _conv_oracle(B, L, Cin, Cout, k, s, padding):
+    rng = np.random.RandomState(B * 1000 + L + Cin + Cout)
+    x = f32(rng.randn(B, L, Cin)); w = f32(rng.randn(k, Cin, Cout) / np.sqrt(k * Cin)); b = f32(rng.randn(Cout))
+    y_ref = K.conv1d_fwd(x, w, b, s, padding)
+    dy = f32(rng.randn(B, y_ref.shape[1], Cout))
+    return (x, w, b, dy, y_ref) + K.conv1d_bwd(x, w, dy, s, padding)
+
+
+@pytest.mark.parametrize("B,L,Cin,Cout,k,s,padding,fams_fp32,fams_wino,math", CF.per_math(CONV_CASES, 7))
+def test_conv1d_fwd_dgrad_wgrad(B, L, Cin, Cout, k, s, padding, fams_fp32, fams_wino, math):
+    """Forward (four activation epilogues), data gradient and weight / bias gradient against the fp64 oracle, under each conv math, each direction
+    asserted to reach the family its row names."""
+    from gennet_amd import ops
+    x, w, b, dy, y_ref, dx_ref, dw_ref, db_ref = _CONV_ORACLE.get((B, L, Cin, Cout, k, s, padding), lambda: _conv_oracle(B, L, Cin, Cout, k, s, padding))
+    f_fwd, f_dgrad, f_wgrad = CF.families(fams_fp32 if math == 'fp32' else fams_wino)
+    Lout, pl = ops.conv_geometry(L, k, s, padding)
+    assert y_ref.shape[1] == Lout
+    xd, wd, bd, dyd = g(x), g(w), g(b), g(dy)
+    with ops.conv_math(math):
+        for act, p in (('linear', 0.0), ('relu', 0.0), ('leaky', 0.2), ('tanh', 0.0)):
+            y = CF.run('fwd', f_fwd, lambda: ops.conv1d_fwd(xd, wd, bd, s, pl, Lout, act, p))
+            close(y, K.act_fwd(y_ref, act, p))
+        wt = ops.conv1d_transpose_w(wd)
+        close(wt, np.transpose(w, (0, 2, 1)), 0.0)
+        dx = CF.run('dgrad', f_dgrad, lambda: ops.conv1d_dgrad(dyd, wt, L, s, pl), s)
+        close(dx, dx_ref)
+        dw, db = CF.run('wgrad', f_wgrad, lambda: ops.conv1d_wgrad(xd, dyd, k, s, pl))
+        close(dw, dw_ref, 5e-5)
+        close(db, db_ref, 5e-5)
+
+
+STATS_CASES = [
+    # B, L, Cin, Cout, stride, padding; forward family under 'fp32', under 'wino'
+    (3, 300, 64, 128, 1, 'same',   'direct', 'wino'),       # pipelined kernel, square tile, ragged last M tile / the F(2,5) epilogue
+    (2, 700, 32, 64, 1, 'same',    'direct', 'wino'),       # tall tile (256 rows), 700 = 2*256 + 188
+    (2, 512, 64, 64, 2, 'same',    'direct', 'wino_s2'),    # stride 2 (de-interleaved slab) / the stride-2 transform-domain epilogue
+    (2, 90, 20, 72, 1, 'valid',    'direct', 'direct'),     # ragged channels: plain kernel + separate statistics pass
+    (2, 64, 2, 16, 1, 'same',      'small', 'small'),       # small-Cin kernel + separate pass
 ]
 
 
-@pytest.mark.parametrize("B,L,Cin,Cout,k,s,padding", CONV_CASES)
-def test_conv1d_fwd_dgrad_wgrad(B, L, Cin, Cout, k, s, padding):
-    from gennet_amd import ops
-    rng = np.random.RandomState(B * 1000 + L + Cin + Cout)
-    x = f32(rng.randn(B, L, Cin)); w = f32(rng.randn(k, Cin, Cout) / np.sqrt(k * Cin)); b = f32(rng.randn(Cout))
-    Lout, pl = ops.conv_geometry(L, k, s, padding)
-    y_ref = K.conv1d_fwd(x, w, b, s, padding)
-    assert y_ref.shape[1] == Lout
-    for act, p in (('linear', 0.0), ('relu', 0.0), ('leaky', 0.2), ('tanh', 0.0)):
-        y = ops.conv1d_fwd(g(x), g(w), g(b), s, pl, Lout, act, p)
-        close(y, K.act_fwd(y_ref, act, p))
-    dy = f32(rng.randn(B, Lout, Cout))
-    dx_ref, dw_ref, db_ref = K.conv1d_bwd(x, w, dy, s, padding)
-    wt = ops.conv1d_transpose_w(g(w))
-    close(wt, np.transpose(w, (0, 2, 1)), 0.0)
-    dx = ops.conv1d_dgrad(g(dy), wt, L, s, pl)
-    close(dx, dx_ref)
-    dw, db = ops.conv1d_wgrad(g(x), g(dy), k, s, pl)
-    close(dw, dw_ref, 5e-5)
-    close(db, db_ref, 5e-5)
+_STATS_ORACLE = CF.OneCase()
 
 
-@pytest.mark.parametrize("B,L,Cin,Cout,s,padding", [(3, 300, 64, 128, 1, 'same'),      # pipelined kernel, square tile, ragged last M tile
-                                                    (2, 700, 32, 64, 1, 'same'),       # tall tile (256 rows), 700 = 2*256 + 188
-                                                    (2, 512, 64, 64, 2, 'same'),       # stride 2 (de-interleaved slab)
-                                                    (2, 90, 20, 72, 1, 'valid'),       # ragged channels: plain kernel + separate statistics pass
-                                                    (2, 64, 2, 16, 1, 'same')])        # small-Cin kernel + separate pass
-def test_conv1d_fwd_with_batchnorm_statistics(B, L, Cin, Cout, s, padding):
+def _stats_oracle(B, L, Cin, Cout, s, padding, seed, bias_mean):
+    rng = np.random.RandomState(seed)
+    x = f32(rng.randn(B, L, Cin)); w = f32(rng.randn(5, Cin, Cout) / np.sqrt(5 * Cin)); b = f32(rng.randn(Cout) * 0.3 + bias_mean)
+    return x, w, b, K.conv1d_fwd(x, w, b, s, padding)
+
+
+@pytest.mark.parametrize("B,L,Cin,Cout,s,padding,fam_fp32,fam_wino,math", CF.per_math(STATS_CASES, 6))
+def test_conv1d_fwd_with_batchnorm_statistics(B, L, Cin, Cout, s, padding, fam_fp32, fam_wino, math):
     """gn_conv1d_fwd_stats: y as gn_conv1d_fwd, sums = (sum y, sum y^2) over (B, Lout) in fp64 -- from the conv epilogue on the pipelined
-    kernel (rows of the ragged last tile excluded), from a separate pass elsewhere."""
+    and the transform-domain kernels (rows of the ragged last tile excluded), from a separate pass elsewhere."""
     from gennet_amd import ops
-    rng = np.random.RandomState(L + Cin)
-    x = f32(rng.randn(B, L, Cin)); w = f32(rng.randn(5, Cin, Cout) / np.sqrt(5 * Cin)); b = f32(rng.randn(Cout) * 0.3 + 0.5)
+    x, w, b, y_ref = _STATS_ORACLE.get((B, L, Cin, Cout, s, padding), lambda: _stats_oracle(B, L, Cin, Cout, s, padding, L + Cin, 0.5))
     Lout, pl = ops.conv_geometry(L, 5, s, padding)
-    y_ref = K.conv1d_fwd(x, w, b, s, padding)
-    y, sums = ops.conv1d_fwd_stats(g(x), g(w), g(b), s, pl, Lout)
-    close(y, y_ref)
-    assert torch.equal(y, ops.conv1d_fwd(g(x), g(w), g(b), s, pl, Lout))
+    fam = fam_fp32 if math == 'fp32' else fam_wino
+    with ops.conv_math(math):
+        y, sums = CF.run('fwd', fam, lambda: ops.conv1d_fwd_stats(g(x), g(w), g(b), s, pl, Lout))
+        close(y, y_ref)
+        assert torch.equal(y, CF.run('fwd', fam, lambda: ops.conv1d_fwd(g(x), g(w), g(b), s, pl, Lout)))
     yd = y.double().reshape(-1, Cout)
     ref = torch.cat([yd.sum(0), (yd * yd).sum(0)]).cpu().numpy()
     got = sums.cpu().numpy()
@@ -118,14 +168,15 @@ def test_conv1d_fwd_with_batchnorm_statistics(B, L, Cin, Cout, s, padding):
     close(ops.bn_stats(y.reshape(-1, Cout)), got, 1e-12)
 
 
-@pytest.mark.parametrize("B,L,Cin,Cout", [(8, 100, 64, 64), (8, 65, 64, 64), (8, 192, 128, 64), (3, 100, 64, 128)])
-def test_conv1d_fwd_stats_stays_inside_an_exact_size_workspace(B, L, Cin, Cout):
+@pytest.mark.parametrize("B,L,Cin,Cout,fam_fp32,fam_wino,math", CF.per_math([(8, 100, 64, 64, 'direct', 'wino'), (8, 65, 64, 64, 'direct', 'wino'),
+                                                                              (8, 192, 128, 64, 'direct', 'wino'), (3, 100, 64, 128, 'direct', 'wino')], 4))
+def test_conv1d_fwd_stats_stays_inside_an_exact_size_workspace(B, L, Cin, Cout, fam_fp32, fam_wino, math):
     """ADVICE r3: the narrow-wave launches of conv_pipe.hip use 64-row blocks, so the fused statistics write B * ceil(Lout / 64) partial rows;
     gn_conv1d_fwd_stats_workspace sized them for 128-row tiles.  An exact-size C-API caller (no slack, unlike ops.workspace) must be safe: the
-    call runs in a buffer of EXACTLY the advertised size followed by a guard region that has to come back untouched."""
+    call runs in a buffer of EXACTLY the advertised size followed by a guard region that has to come back untouched -- on the direct kernels
+    (the narrow-wave partials of conv_pipe) and on the transform-domain kernel (its own partials), both against the one advertised size."""
     from gennet_amd import _lib, ops
-    rng = np.random.RandomState(B * L + Cout)
-    x = f32(rng.randn(B, L, Cin)); w = f32(rng.randn(5, Cin, Cout) / np.sqrt(5 * Cin)); b = f32(rng.randn(Cout) * 0.3)
+    x, w, b, y_ref = _STATS_ORACLE.get((B, L, Cin, Cout), lambda: _stats_oracle(B, L, Cin, Cout, 1, 'same', B * L + Cout, 0.0))
     Lout, pl = ops.conv_geometry(L, 5, 1, 'same')
     nb = _lib.size('gn_conv1d_fwd_stats_workspace', B, Lout, Cout)
     assert nb >= B * -(-Lout // 64) * 2 * Cout * 8
@@ -134,10 +185,12 @@ def test_conv1d_fwd_stats_stays_inside_an_exact_size_workspace(B, L, Cin, Cout):
     xd, wd, bd = g(x), g(w), g(b)
     y = torch.empty((B, Lout, Cout), dtype=torch.float32, device='cuda')
     sums = torch.empty((2 * Cout,), dtype=torch.float64, device='cuda')
-    _lib.call('gn_conv1d_fwd_stats', ops._p(xd), ops._p(wd), ops._p(bd), ops._p(y), ops._p(sums), ops._p(buf), nb, B, L, Cin, Cout, 5, 1, pl, Lout, ops._stream())
+    with ops.conv_math(math):
+        CF.run('fwd', fam_fp32 if math == 'fp32' else fam_wino, lambda: _lib.call('gn_conv1d_fwd_stats', ops._p(xd), ops._p(wd), ops._p(bd), ops._p(y), ops._p(sums), ops._p(buf), nb,
+                                                B, L, Cin, Cout, 5, 1, pl, Lout, ops._stream()))
     torch.cuda.synchronize()
     assert bool((buf[nb:] == 0xA5).all()), 'statistics partials written past the advertised workspace size'
-    close(y, K.conv1d_fwd(x, w, b, 1, 'same'))
+    close(y, y_ref)
     yd = y.double().reshape(-1, Cout)
     ref = torch.cat([yd.sum(0), (yd * yd).sum(0)]).cpu().numpy()
     assert np.abs(sums.cpu().numpy() - ref).max() <= 1e-12 * np.abs(ref).max()
@@ -453,35 +506,30 @@ def test_bad_arguments_raise_not_crash():
 
 
 FULL_SIZE_LAYERS = [
-    # the BASELINE-size layer shapes of the three networks at n_pix = 2048: (L, Cin, Cout, stride, padding)
-    (2048, 512, 1024, 1, 'same'),      # generator conv5 (74 % of G)
-    (1018, 512, 1024, 2, 'valid'),     # point-estimator q-branch conv5
-    (2040, 256, 512, 2, 'valid'),      # q-branch conv4
-    (1024, 512, 1024, 2, 'same'),      # discriminator conv2 after the width-2 fold
-    (2048, 1024, 1, 1, 'same'),        # generator output conv
-    (2048, 2, 512, 2, 'same'),         # discriminator conv1 after the fold
+    # the BASELINE-size layer shapes of the three networks at n_pix = 2048: (L, Cin, Cout, stride, padding);
+    # the family of each direction (fwd dgrad wgrad) under 'fp32' and under 'wino'
+    (2048, 512, 1024, 1, 'same',    'direct direct direct', 'wino wino wino'),              # generator conv5 (74 % of G)
+    (1018, 512, 1024, 2, 'valid',   'direct merged direct', 'wino_s2 wino_s2 wino_s2'),     # point-estimator q-branch conv5
+    (2040, 256, 512, 2, 'valid',    'direct merged direct', 'wino_s2 wino_s2 wino_s2'),     # q-branch conv4
+    (1024, 512, 1024, 2, 'same',    'direct merged direct', 'wino_s2 wino_s2 wino_s2'),     # discriminator conv2 after the width-2 fold
+    (2048, 1024, 1, 1, 'same',      'small small small', 'small small small'),              # generator output conv
+    (2048, 2, 512, 2, 'same',       'small small small', 'small small small'),              # discriminator conv1 after the fold
 ]
 
+_FULL_SIZE_POINTS = CF.OneCase()
 
-@pytest.mark.parametrize("L,Cin,Cout,s,padding", FULL_SIZE_LAYERS)
-def test_full_size_layers_spot_checked_against_the_definition(L, Cin, Cout, s, padding):
-    """Full BASELINE layer shapes: the oracle cannot run them whole in seconds, so 300 randomly chosen output / gradient elements
-    are recomputed in fp64 straight from the definition y[b,t,co] = bias + sum_{k,ci} x[b, s t + k - pl, ci] w[k,ci,co]
-    (and its two adjoints).  Tolerance 2e-5 of the output scale (K up to 2560-term fp32 chains)."""
+
+def _full_size_points(L, Cin, Cout, s, padding):
+    """Inputs, and 300 output / data-gradient elements and 40 weight-gradient elements recomputed in fp64 straight from the definition
+    y[b,t,co] = bias + sum_{k,ci} x[b, s t + k - pl, ci] w[k,ci,co] and its two adjoints: [(index, value)] per direction."""
     from gennet_amd import ops
     rng = np.random.RandomState(L + Cin)
     B, k = 3, 5
     x = rng.randn(B, L, Cin).astype(np.float32); w = (rng.randn(k, Cin, Cout) / np.sqrt(k * Cin)).astype(np.float32); b = rng.randn(Cout).astype(np.float32)
     Lout, pl = ops.conv_geometry(L, k, s, padding)
-    xd, wd = g(x), g(w)
-    y = ops.conv1d_fwd(xd, wd, g(b), s, pl, Lout).cpu().numpy()
     dy = rng.randn(B, Lout, Cout).astype(np.float32)
-    dyd = g(dy)
-    dx = ops.conv1d_dgrad(dyd, ops.conv1d_transpose_w(wd), L, s, pl).cpu().numpy()
-    dw, db = ops.conv1d_wgrad(xd, dyd, k, s, pl)
-    dw = dw.cpu().numpy(); db = db.cpu().numpy()
     x64, w64, dy64 = x.astype(np.float64), w.astype(np.float64), dy.astype(np.float64)
-    ys = np.abs(y).max(); dxs = np.abs(dx).max(); dws = np.abs(dw).max()
+    ys, dxs, dws = [], [], []
     for _ in range(300):
         bb, t, co = rng.randint(B), rng.randint(Lout), rng.randint(Cout)
         acc = float(b[co])
@@ -489,23 +537,44 @@ def test_full_size_layers_spot_checked_against_the_definition(L, Cin, Cout, s, p
             tt = s * t + kk - pl
             if 0 <= tt < L:
                 acc += x64[bb, tt] @ w64[kk, :, co]
-        assert abs(y[bb, t, co] - acc) <= 2e-5 * ys
+        ys.append(((bb, t, co), acc))
         tau, ci = rng.randint(L), rng.randint(Cin)
         acc = 0.0
         for kk in range(k):
             num = tau + pl - kk
             if num % s == 0 and 0 <= num // s < Lout:
                 acc += dy64[bb, num // s] @ w64[kk, ci]
-        assert abs(dx[bb, tau, ci] - acc) <= 2e-5 * dxs
+        dxs.append(((bb, tau, ci), acc))
     for _ in range(40):
         kk, ci, co = rng.randint(k), rng.randint(Cin), rng.randint(Cout)
         ts_ = np.arange(Lout); src = s * ts_ + kk - pl
         ok = (src >= 0) & (src < L)
-        acc = sum(x64[bb, src[ok], ci] @ dy64[bb, ts_[ok], co] for bb in range(B))
-        assert abs(dw[kk, ci, co] - acc) <= 5e-5 * dws
-    assert np.abs(db - dy64.sum(axis=(0, 1))).max() <= 5e-5 * np.abs(db).max()
+        dws.append(((kk, ci, co), sum(x64[bb, src[ok], ci] @ dy64[bb, ts_[ok], co] for bb in range(B))))
+    return x, w, b, dy, ys, dxs, dws, dy64.sum(axis=(0, 1))
 
 
+@pytest.mark.parametrize("L,Cin,Cout,s,padding,fams_fp32,fams_wino,math", CF.per_math(FULL_SIZE_LAYERS, 5))
+def test_full_size_layers_spot_checked_against_the_definition(L, Cin, Cout, s, padding, fams_fp32, fams_wino, math):
+    """Full BASELINE layer shapes under each conv math: the oracle cannot run them whole in seconds, so 300 randomly chosen output / gradient
+    elements are recomputed in fp64 from the definition (once per layer, shared by the maths).  Tolerance 2e-5 of the output scale (K up to
+    2560-term fp32 chains), 5e-5 for the weight and bias gradients."""
+    from gennet_amd import ops
+    x, w, b, dy, ys, dxs, dws, db_ref = _FULL_SIZE_POINTS.get((L, Cin, Cout, s, padding), lambda: _full_size_points(L, Cin, Cout, s, padding))
+    f_fwd, f_dgrad, f_wgrad = CF.families(fams_fp32 if math == 'fp32' else fams_wino)
+    k = 5
+    Lout, pl = ops.conv_geometry(L, k, s, padding)
+    xd, wd, dyd = g(x), g(w), g(dy)
+    with ops.conv_math(math):
+        y = CF.run('fwd', f_fwd, lambda: ops.conv1d_fwd(xd, wd, g(b), s, pl, Lout)).cpu().numpy()
+        wt = ops.conv1d_transpose_w(wd)
+        dx = CF.run('dgrad', f_dgrad, lambda: ops.conv1d_dgrad(dyd, wt, L, s, pl), s).cpu().numpy()
+        dw, db = CF.run('wgrad', f_wgrad, lambda: ops.conv1d_wgrad(xd, dyd, k, s, pl))
+    dw = dw.cpu().numpy(); db = db.cpu().numpy()
+    for out, points, tol in ((y, ys, 2e-5), (dx, dxs, 2e-5), (dw, dws, 5e-5)):
+        scale = np.abs(out).max()
+        for idx, ref in points:
+            assert abs(out[idx] - ref) <= tol * scale, (idx, float(out[idx]), ref, scale)
+    assert np.abs(db - db_ref).max() <= 5e-5 * np.abs(db).max()
 
 
 @pytest.mark.parametrize("B,H,W,C", [(3, 32, 2, 256), (2, 7, 2, 5), (1, 2, 1, 1), (4, 1024, 2, 64)])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_family as CF
 from oracle import keras_ref as K
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +31,7 @@ def rel(t, ref):
 
 CASES = [
     # B, L, Cin, Cout, k, stride, padding
-    (2, 64, 64, 64, 10, 1, 'same'),       # pad_left 4: taps 0-4 on x shifted left by 4, taps 5-9 on x shifted right by 1; 5 taps x 128 channels: transform-domain kernel
+    (2, 64, 64, 64, 10, 1, 'same'),       # pad_left 4: taps 0-4 on x shifted left by 4, taps 5-9 on x shifted right by 1; 5 taps x 128 channels: transform-domain kernel under 'wino'
     (3, 133, 64, 128, 10, 1, 'valid'),
     (2, 150, 128, 64, 10, 2, 'same'),     # stride 2: the even/odd-row kernels on the folded input
     (3, 133, 64, 128, 10, 2, 'valid'),
@@ -47,32 +48,43 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("B,L,Cin,Cout,k,stride,padding", CASES)
-def test_conv_6_to_10_taps_against_oracle(B, L, Cin, Cout, k, stride, padding):
+_ORACLE = CF.OneCase()
+
+
+def _oracle(B, L, Cin, Cout, k, stride, padding):
     from gennet_amd import ops
     rng = np.random.RandomState(13 * L + k + stride)
     x = f32(rng.randn(B, L, Cin)); lim = np.sqrt(6.0 / (k * (Cin + Cout)))
     w = f32(rng.uniform(-lim, lim, (k, Cin, Cout))); b = f32(rng.randn(Cout) * 0.1)
     Lout, pl = ops.conv_geometry(L, k, stride, padding)
-    G, h = ops.tap_groups(k)
     y_ref = np.tanh(K.conv1d_fwd(x, w, b, stride, padding))
     dy = f32(rng.randn(B, Lout, Cout))
-    dx_ref, dw_ref, db_ref = K.conv1d_bwd(x, w, dy, stride, padding)
-    # the fold kernels: pure data movement, bit for bit against numpy
-    x2 = ops.conv1d_tapfold_x(g(x), k, pl)
-    xp = np.zeros((B, L + pl + G * h, Cin)); xp[:, pl:pl + L] = x
-    assert np.array_equal(x2.cpu().numpy(), np.concatenate([xp[:, gi * h:gi * h + L + pl] for gi in range(G)], axis=2).astype(np.float32))
-    w2 = ops.conv1d_tapfold_w(g(w))
-    wp = np.zeros((G * h, Cin, Cout)); wp[:k] = w
-    assert np.array_equal(w2.cpu().numpy(), np.concatenate([wp[gi * h:(gi + 1) * h] for gi in range(G)], axis=1).astype(np.float32))
-    assert np.array_equal(ops.conv1d_tapunfold_dw(w2, k).cpu().numpy(), w.astype(np.float32))
-    # forward, data gradient, weight gradient through the h-tap kernels
-    y = ops.conv1d_fwd(x2, w2, g(b), stride, 0, Lout, 'tanh')
-    assert rel(y, y_ref) <= RTOL
-    dx2 = ops.conv1d_dgrad(g(dy), ops.conv1d_transpose_w(w2), L + pl, stride, 0)
-    assert rel(ops.conv1d_tapunfold_dx(dx2, L, k, pl), dx_ref) <= RTOL
-    dw2, db = ops.conv1d_wgrad(x2, g(dy), h, stride, 0)
-    assert rel(ops.conv1d_tapunfold_dw(dw2, k), dw_ref) <= RTOL and rel(db, db_ref) <= 1e-6
+    return (x, w, b, dy, y_ref) + K.conv1d_bwd(x, w, dy, stride, padding)
+
+
+@pytest.mark.parametrize("B,L,Cin,Cout,k,stride,padding,math", CF.per_math(CASES, 7))
+def test_conv_6_to_10_taps_against_oracle(B, L, Cin, Cout, k, stride, padding, math):
+    """Under each conv math (the oracle computed once per case): the folded layer reaches whichever family the selector gives its h-tap shape."""
+    from gennet_amd import ops
+    x, w, b, dy, y_ref, dx_ref, dw_ref, db_ref = _ORACLE.get((B, L, Cin, Cout, k, stride, padding), lambda: _oracle(B, L, Cin, Cout, k, stride, padding))
+    Lout, pl = ops.conv_geometry(L, k, stride, padding)
+    G, h = ops.tap_groups(k)
+    with ops.conv_math(math):
+        # the fold kernels: pure data movement, bit for bit against numpy
+        x2 = ops.conv1d_tapfold_x(g(x), k, pl)
+        xp = np.zeros((B, L + pl + G * h, Cin)); xp[:, pl:pl + L] = x
+        assert np.array_equal(x2.cpu().numpy(), np.concatenate([xp[:, gi * h:gi * h + L + pl] for gi in range(G)], axis=2).astype(np.float32))
+        w2 = ops.conv1d_tapfold_w(g(w))
+        wp = np.zeros((G * h, Cin, Cout)); wp[:k] = w
+        assert np.array_equal(w2.cpu().numpy(), np.concatenate([wp[gi * h:(gi + 1) * h] for gi in range(G)], axis=1).astype(np.float32))
+        assert np.array_equal(ops.conv1d_tapunfold_dw(w2, k).cpu().numpy(), w.astype(np.float32))
+        # forward, data gradient, weight gradient through the h-tap kernels
+        y = ops.conv1d_fwd(x2, w2, g(b), stride, 0, Lout, 'tanh')
+        assert rel(y, y_ref) <= RTOL
+        dx2 = ops.conv1d_dgrad(g(dy), ops.conv1d_transpose_w(w2), L + pl, stride, 0)
+        assert rel(ops.conv1d_tapunfold_dx(dx2, L, k, pl), dx_ref) <= RTOL
+        dw2, db = ops.conv1d_wgrad(x2, g(dy), h, stride, 0)
+        assert rel(ops.conv1d_tapunfold_dw(dw2, k), dw_ref) <= RTOL and rel(db, db_ref) <= 1e-6
 
 
 def test_unit_stride_10_taps_take_the_transform_domain_kernels():

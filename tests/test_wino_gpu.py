@@ -388,7 +388,8 @@ def test_weight_gradient_against_oracle_and_direct_kernel(B, L, Cin, Cout, strid
 
 def test_random_shapes_agree_with_the_direct_kernels():
     """60 random launches (both strides and paddings, odd chunk counts, ragged row and column tiles, 1-row inputs) of forward, data gradient and weight
-    gradient: transform-domain against direct kernels at the kernels' tolerance -- the direct kernels being the ones every other test file pins on the oracle."""
+    gradient: transform-domain against direct kernels at the kernels' tolerance.  Both families are pinned on the oracle separately: the conv
+    parity tables of tests/test_kernels_gpu.py, test_tapfold_gpu.py and test_edges_gpu.py run every case under 'fp32' and under 'wino'."""
     from gennet_amd import ops
     rng = np.random.RandomState(2025)
     dev = torch.device('cuda:0')
