@@ -8,9 +8,13 @@ One "step" pushes WAVES = 512 synthetic waveforms per GPU through BOTH training 
 so value = N_gpus * 512 * steps / wall_time = B / (t_CNN + t_GAN) of SURVEY section 8d.  Inputs (template bank, labels, event)
 are resident in HBM before the timed region; every optimizer step, BatchNorm update and dropout draw is inside it.
 
-python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 K timed steps after W warm-up steps; ms_per_step in the line is the wall time of one timed step.  --dump-outputs writes what the last
 timed step computed to DIR/*.npy (dump_outputs); the inputs are seeded, so two builds run with the same arguments compare output for output.
+A plain run does only what the headline needs: set up, warm up, time the K steps, check their losses, print the line (with the roofline
+figures the timed steps' own launch events give).  --full also runs what takes runs of its own after the timed steps: the CNN / GAN /
+synthesiser breakdown, the synthesiser roofline, the CPU baseline (N = 1, unless --no-cpu-baseline), the measured exchange step and its
+check (N > 1) and, with --opt-in, the bf16-split leg.
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a
 rank; started plainly it launches `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a CHILD process
 before anything here touches the GPU, relays the child's output and exits with its code.  A rank whose world size differs from
@@ -206,11 +210,14 @@ def main():
                          "refdefaults: the reference script's own batch 8 / n_pix 1024 (not a BASELINE config), loop bodies replayed as hipGraphs")
     ap.add_argument('--no-graph', action='store_true', help='refdefaults: run the loop bodies eagerly instead of replaying captured hipGraphs')
     ap.add_argument('--predict-batch', type=int, default=0, help='chunk size of generator.predict for the fake half (0: the GAN batch)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure and check what takes runs of its own: the CNN / GAN / synthesiser '
+                                                        'breakdown, the synthesiser roofline, the CPU baseline (N = 1), the exchange step (N > 1); '
+                                                        'a plain run prints the headline line alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--batch-scale', type=int, default=1, help='multiply the per-GPU batch sizes: `--gpus 1 --batch-scale N` runs the GLOBAL batch of an N-GPU '
                                                                 'job on one GPU -- its last_losses are what `--gpus N` prints (same draws, rank-tiled)')
-    ap.add_argument('--opt-in', action='store_true', help='after the headline numbers are final, time the same K steps under the opt-in bf16-split conv math in a '
-                                                          'CHILD process (its failure, hang or fault becomes opt_in.error; never part of value)')
+    ap.add_argument('--opt-in', action='store_true', help='with --full: after the headline numbers are final, time the same K steps under the opt-in bf16-split conv '
+                                                          'math in a CHILD process (its failure, hang or fault becomes opt_in.error; never part of value)')
     ap.add_argument('--no-opt-in', action='store_true', help='(accepted for old command lines; the extra leg is off unless --opt-in is given)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): its losses and the trained '
@@ -220,6 +227,8 @@ def main():
         ap.error('--gpus must be >= 1')
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.opt_in and not args.full:
+        ap.error('--opt-in is part of a --full run')
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -332,7 +341,8 @@ def main():
         sys.stderr.write('bench.py: rank %d: the last step returned non-finite or out-of-range losses (%s): %r\n' % (rank, bad, last_losses))
         sys.exit(3)
 
-    # SURVEY 8d also asks for the two loops and the synthesiser separately: timed AFTER the K steps (not part of `value`)
+    # --full only from here to the line: runs of their own after the K steps (not part of `value`)
+    # SURVEY 8d also asks for the two loops and the synthesiser separately: timed AFTER the K steps
     def timed(fn, reps):
         barrier()
         t = time.perf_counter()
@@ -340,11 +350,12 @@ def main():
             fn()
         barrier()
         return (time.perf_counter() - t) / reps
-    t_cnn = timed(cnn_step, 4)
-    t_gan = timed(gan_step, 2)
+    if args.full:
+        t_cnn = timed(cnn_step, 4)
+        t_gan = timed(gan_step, 2)
     # N > 1: the exchange step measured, not estimated -- one more step with every all-reduce bracketed by HIP events on the launch stream
     coll = None
-    if dp:
+    if dp and args.full:
         dp.reset_counters(); dp.timing = True
         barrier()
         t = time.perf_counter()
@@ -368,14 +379,15 @@ def main():
     # whiten -> both inverse FFTs -> arg-max -> slide -> crop, one kernel); cfg5: the launch the CNN loop makes -- the same plus gen_noise ->
     # whiten_data('td') -> crop -> add in the same workgroup.  Priced twice: fp64 VALU operations (what bounds it) and SURVEY 8d's byte figure.
     SYN_NB = 16384
-    syn_bank = online if wl['online'] else synth
-    syn_bank.draw(1024)
-    ops.prof_enable(True); ops.prof_reset()
-    t_syn = timed(lambda: syn_bank.draw(SYN_NB), 3)
-    ops.prof_enable(False)
-    syn = ops.prof_collect(3)
     nz = None
-    if wl['online']:
+    if args.full:
+        syn_bank = online if wl['online'] else synth
+        syn_bank.draw(1024)
+        ops.prof_enable(True); ops.prof_reset()
+        t_syn = timed(lambda: syn_bank.draw(SYN_NB), 3)
+        ops.prof_enable(False)
+        syn = ops.prof_collect(3)
+    if args.full and wl['online']:
         ops.prof_enable(True); ops.prof_reset()
         timed(lambda: online.draw_noise(SYN_NB), 3)
         ops.prof_enable(False)
@@ -396,12 +408,11 @@ def main():
                  'alg': wgwino['flop'] / WINO_RATIO + wgwino2['flop'] / WINO2_RATIO, 'bytes': wgwino['bytes'] + wgwino2['bytes']}
         ach = fam_exec / (fam_ms * 1e-3) / 1e12 if fam_ms > 0 else 0.0
         traffic, traffic_src, traffic_why = pmc_traffic_per_launch((conv['launches'], n_td))
-        syn_tbs = syn['bytes'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0
         out = {
             'metric': 'waveforms/sec (CNN+GAN step, %d-sample BBH)' % N_PIX, 'value': value, 'unit': 'waveforms/s',
             'n_gpus': world, 'ranks': world, 'collective_backend': ('rccl' if backend == 'nccl' else backend) if dp else None, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': args.full,
             'last_losses': last_losses,
             'collectives': coll,
             'config': {'workload': ('BASELINE %s; per GPU and step: %d x CNN point-estimator train_on_batch(batch=%d) + 1 GAN iteration(batch=%d) '
@@ -461,31 +472,33 @@ def main():
                                           'timed region (two hipEventRecord per launch, ~%d launches per step): their cost is included in value, i.e. counts '
                                           'against this line' % ((conv['launches'] + n_td + wgrad['launches'] + wg_td['launches']) // max(args.steps, 1)),
                          'step_algorithmic_tflops': world * WAVES * args.steps * (wl['gflop_cnn'] + wl['gflop_gan']) * 1e-3 / dt},
-            'roofline_synth': {'bound': 'valu_f64', 'kernel': 'synth_fused_kernel<.., NOISE=%s> (%s)' % (('true', 'gn_synth_templates_noise: prior + template + coloured whitened noise')
-                                                                                                         if wl['online'] else ('false', 'gn_synth_templates_prior')),
-                               'achieved': syn['flop'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0, 'peak': PEAK_F64_VALU_TFLOPS, 'unit': 'TFLOP/s',
-                               'frac': (syn['flop'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0) / PEAK_F64_VALU_TFLOPS, 'traffic': None,
-                               'rows_per_launch': SYN_NB, 'launches': syn['launches'], 'avg_launch_ms': syn['ms'] / max(syn['launches'], 1),
-                               'algorithmic_f64_flop_per_row': syn['flop'] / max(syn['launches'], 1) / SYN_NB,
-                               'algorithmic_bytes_per_row': syn['bytes'] / max(syn['launches'], 1) / SYN_NB,
-                               'algorithmic_equivalent_TBps': syn_tbs, 'algorithmic_equivalent_frac_of_hbm_peak': syn_tbs / PEAK_HBM_TBS,
-                               'kernel_rows_per_s': syn['launches'] * SYN_NB / (syn['ms'] * 1e-3) if syn['ms'] > 0 else 0.0,
-                               'launches_inside_timed_steps': syn_in_step['launches'], 'ms_inside_timed_steps': syn_in_step['ms'],
-                               'noise_kernel': None if nz is None else {
-                                   'kernel': 'noise_whitened_kernel (gn_noise_whitened: gen_noise -> whiten_data(td) -> crop)', 'launches': nz['launches'],
-                                   'avg_launch_ms': nz['ms'] / max(nz['launches'], 1), 'achieved': nz['flop'] / (nz['ms'] * 1e-3) / 1e12 if nz['ms'] > 0 else 0.0,
-                                   'frac': (nz['flop'] / (nz['ms'] * 1e-3) / 1e12 if nz['ms'] > 0 else 0.0) / PEAK_F64_VALU_TFLOPS,
-                                   'kernel_rows_per_s': nz['launches'] * SYN_NB / (nz['ms'] * 1e-3) if nz['ms'] > 0 else 0.0},
-                               'note': 'the kernel keeps spectra and series in registers / LDS and writes only the output row, so fp64 vector arithmetic (and LDS traffic) '
-                                       'bounds it, not HBM: achieved = counted fp64 operations (transforms 5 M log2 M each, ~150 per spectrum bin, Box-Muller ~120 per noise '
-                                       'bin; csrc/synth_fused.hip, noise_fused.hip) / kernel time against the fp64 vector peak.  algorithmic_equivalent_TBps prices the '
-                                       'same launches with the SURVEY 8d byte figure (spectra + PSD + window read, row written) -- traffic the fused kernel never issues'},
-            'breakdown': {'cnn_train_waveforms_per_s': world * CNN_BATCH / t_cnn, 'gan_iteration_waveforms_per_s': world * GAN_BATCH / t_gan,
-                          'cnn_ms_per_batch': 1e3 * t_cnn, 'gan_ms_per_iteration': 1e3 * t_gan,
-                          'synth_templates_per_s': world * SYN_NB / t_syn,
-                          'note': 'rank-0 clock, measured after the timed steps; value = B / (t_CNN + t_GAN) comes from the K timed steps only; '
-                                  'synth_templates_per_s = OnlineBank.draw wall clock of the launch priced in roofline_synth (no host random numbers)'},
         }
+        if args.full:
+            syn_tbs = syn['bytes'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0
+            out['roofline_synth'] = {'bound': 'valu_f64', 'kernel': 'synth_fused_kernel<.., NOISE=%s> (%s)' % (('true', 'gn_synth_templates_noise: prior + template + coloured whitened noise')
+                                                                                                               if wl['online'] else ('false', 'gn_synth_templates_prior')),
+                                     'achieved': syn['flop'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0, 'peak': PEAK_F64_VALU_TFLOPS, 'unit': 'TFLOP/s',
+                                     'frac': (syn['flop'] / (syn['ms'] * 1e-3) / 1e12 if syn['ms'] > 0 else 0.0) / PEAK_F64_VALU_TFLOPS, 'traffic': None,
+                                     'rows_per_launch': SYN_NB, 'launches': syn['launches'], 'avg_launch_ms': syn['ms'] / max(syn['launches'], 1),
+                                     'algorithmic_f64_flop_per_row': syn['flop'] / max(syn['launches'], 1) / SYN_NB,
+                                     'algorithmic_bytes_per_row': syn['bytes'] / max(syn['launches'], 1) / SYN_NB,
+                                     'algorithmic_equivalent_TBps': syn_tbs, 'algorithmic_equivalent_frac_of_hbm_peak': syn_tbs / PEAK_HBM_TBS,
+                                     'kernel_rows_per_s': syn['launches'] * SYN_NB / (syn['ms'] * 1e-3) if syn['ms'] > 0 else 0.0,
+                                     'launches_inside_timed_steps': syn_in_step['launches'], 'ms_inside_timed_steps': syn_in_step['ms'],
+                                     'noise_kernel': None if nz is None else {
+                                         'kernel': 'noise_whitened_kernel (gn_noise_whitened: gen_noise -> whiten_data(td) -> crop)', 'launches': nz['launches'],
+                                         'avg_launch_ms': nz['ms'] / max(nz['launches'], 1), 'achieved': nz['flop'] / (nz['ms'] * 1e-3) / 1e12 if nz['ms'] > 0 else 0.0,
+                                         'frac': (nz['flop'] / (nz['ms'] * 1e-3) / 1e12 if nz['ms'] > 0 else 0.0) / PEAK_F64_VALU_TFLOPS,
+                                         'kernel_rows_per_s': nz['launches'] * SYN_NB / (nz['ms'] * 1e-3) if nz['ms'] > 0 else 0.0},
+                                     'note': 'the kernel keeps spectra and series in registers / LDS and writes only the output row, so fp64 vector arithmetic (and LDS traffic) '
+                                             'bounds it, not HBM: achieved = counted fp64 operations (transforms 5 M log2 M each, ~150 per spectrum bin, Box-Muller ~120 per noise '
+                                             'bin; csrc/synth_fused.hip, noise_fused.hip) / kernel time against the fp64 vector peak.  algorithmic_equivalent_TBps prices the '
+                                             'same launches with the SURVEY 8d byte figure (spectra + PSD + window read, row written) -- traffic the fused kernel never issues'}
+            out['breakdown'] = {'cnn_train_waveforms_per_s': world * CNN_BATCH / t_cnn, 'gan_iteration_waveforms_per_s': world * GAN_BATCH / t_gan,
+                                'cnn_ms_per_batch': 1e3 * t_cnn, 'gan_ms_per_iteration': 1e3 * t_gan,
+                                'synth_templates_per_s': world * SYN_NB / t_syn,
+                                'note': 'rank-0 clock, measured after the timed steps; value = B / (t_CNN + t_GAN) comes from the K timed steps only; '
+                                        'synth_templates_per_s = OnlineBank.draw wall clock of the launch priced in roofline_synth (no host random numbers)'}
         conv_math = ops.default_conv_math()
         out['config']['conv_math'] = conv_math      # 'wino' (default: transform-domain fp32 on the unit-stride 5-tap layers) | 'fp32' (direct kernels only) | 'bf16x3'
         if conv_math == 'bf16x3':      # the opt-in experiment: say so in the line; never the default configuration
@@ -503,7 +516,7 @@ def main():
             out['roofline']['mfma_kernel_time_share'] = None
             out['roofline']['note'] = ('loop bodies replayed as hipGraphs: the launch-stream HIP events of the eager path are not captured, so per-kernel '
                                        'figures are not measured here; the same command with --no-graph measures them (eager, same losses bit for bit)')
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(N_PIX, CNN_BATCH, GAN_BATCH)
         print(json.dumps(out), flush=True)           # the ONE line the driver parses: printed before anything experimental runs
         if args.opt_in and world == 1 and not graphed and conv_math != 'bf16x3':

@@ -234,6 +234,15 @@ def test_bench_dump_outputs_writes_the_last_steps_results(tmp_path):
     assert r.returncode == 2 and '--steps' in r.stderr
 
 
+def test_bench_opt_in_leg_is_part_of_a_full_run():
+    """The bf16-split leg measures beyond the headline, so a plain run refuses --opt-in (before anything touches the GPU); --full takes it."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--opt-in'], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 2 and '--full' in r.stderr and not r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0 and '--full' in r.stdout and '--opt-in' in r.stdout
+
+
 def test_synth_host_helpers_match_reference_golden():
     from gennet_amd import templates as T
     for key, (M, alpha) in {'tukey_2184': (2184, 1 / 8.), 'tukey_4369': (4369, 1 / 8.), 'tukey_8738': (8738, 1 / 8.), 'tukey_64_half': (64, 0.5)}.items():

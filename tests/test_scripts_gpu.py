@@ -1,6 +1,7 @@
 """End to end, as a BBH_version/ user would run it: scripts/make_templates.py (gw_template_maker.main, gw_template_maker.py:743-865)
 writes the ts / params / event pickles, scripts/bbh_train.py (bbhMahoGANy.main, bbhMahoGANy.py:959-1382) reads them, trains the CNN
 and the GAN on the GPU and leaves the reference's output files behind."""
+import json
 import os
 import pickle
 import subprocess
@@ -17,6 +18,26 @@ def run(args, cwd):
     r = subprocess.run([sys.executable] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_full_line(tmp_path):
+    """bench.py at the headline batch sizes: a plain run prints the headline line with nothing measured after the timed steps; --full adds
+    the CNN / GAN / synthesiser breakdown and the synthesiser roofline (the CPU baseline, minutes on the host, is left out here)."""
+    args = [os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1', '--bank', '4096']
+    plain, full = [json.loads([l for l in run(args + extra, str(tmp_path)).splitlines() if l.startswith('{')][-1])
+                   for extra in ([], ['--full', '--no-cpu-baseline'])]
+    for d in (plain, full):
+        assert d['unit'] == 'waveforms/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and (d['steps'], d['warmup']) == (1, 1)
+        assert abs(d['value'] - d['config']['waveforms_per_step_per_gpu'] * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+        assert d['roofline']['launches'] > 0 and 0.0 < d['roofline']['frac'] < 1.0
+    assert plain['full'] is False and not {'breakdown', 'roofline_synth', 'cpu_baseline', 'opt_in'} & set(plain)
+    assert full['full'] is True and 'cpu_baseline' not in full
+    assert full['breakdown']['cnn_ms_per_batch'] > 0 and full['breakdown']['gan_ms_per_iteration'] > 0 and full['breakdown']['synth_templates_per_s'] > 0
+    assert full['roofline_synth']['launches'] > 0 and full['roofline_synth']['achieved'] > 0
+    # the same seeded warm-up and timed step in both runs: --full changes nothing before the line
+    for k, v in plain['last_losses'].items():
+        assert np.allclose(v, full['last_losses'][k], rtol=1e-4, atol=1e-6), (k, v, full['last_losses'][k])
 
 
 @pytest.mark.gpu
