@@ -41,6 +41,8 @@ _SIGS = {
     'gn_set_conv_math': [i32, vp, sz],
     'gn_conv_fold_bn': [vp, vp, vp, vp, vp, vp, sz, i32, vp],
     'gn_bn_apply_dropgen': [vp, vp, vp, vp, vp, sz, i32, i32, f32, f32, u64, u64, vp],
+    'gn_bias_act_dropout': [vp, vp, vp, sz, i32, i32, f32, f32, i32, u64, u64, vp],
+    'gn_bias_grad': [vp, vp, vp, sz, sz, i32, vp],
     'gn_prelu_fwd': [vp, vp, vp, i32, sz, vp],
     'gn_prelu_bwd': [vp, vp, vp, vp, vp, i32, sz, vp],
     'gn_dropout_mask': [vp, sz, f32, u64, u64, vp],
@@ -106,6 +108,7 @@ _SIZE_FNS = {
     'gn_conv1d_wgrad_workspace': [i32, i32, i32, i32, i32, i32, i32],
     'gn_dense_bwd_workspace': [i32, i32, i32],
     'gn_bn_stats_workspace': [sz, i32],
+    'gn_bias_grad_workspace': [sz, i32],
     'gn_conv1d_fwd_stats_workspace': [i32, i32, i32],
     'gn_optim_sumsq_slots': [sz],
 }

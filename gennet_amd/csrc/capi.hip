@@ -237,14 +237,14 @@ __global__ void f64_to_f32_small_kernel(const double* __restrict__ a, float* __r
   if ((int)threadIdx.x < n) o[threadIdx.x] = (float)a[threadIdx.x];
 }
 
-// db[c] = sum over rows of dy[row, c]; ws needs colred_workspace_bytes(rows, C) (C % 4 == 0) or 32 bytes otherwise
+// db[c] = sum over rows of dy[row, c]; ws needs colred_workspace_bytes(rows, C) (C % 4 == 0 or C > 4) or 32 bytes otherwise.  C > 4 runs
+// the fixed-order column reduction (colred_run: its any-C kernel when C % 4 != 0), so repeated runs are bit-identical.
 static int bias_grad(const float* dy, float* db, size_t rows, int C, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (C % 4 == 0) {
+  if (C % 4 == 0 || C > 4) {
     ColRedArgs r = {};
     r.a = dy; r.rows = rows; r.C = C;
     return colred_run(0, r, ws, ws_bytes, nullptr, db, s);
   }
-  if (C > 4) { set_error("bias_grad: C %d unsupported", C); return GN_EINVAL; }
   if (ws_bytes < 32) { set_error("bias_grad: workspace too small"); return GN_EWORKSPACE; }
   (void)hipMemsetAsync(ws, 0, 32, s);
   size_t g = (rows * C + 255) / 256;
@@ -254,7 +254,38 @@ static int bias_grad(const float* dy, float* db, size_t rows, int C, void* ws, s
   return check_launch("bias_grad");
 }
 
-static size_t bias_grad_ws(size_t rows, int C) { return C % 4 == 0 ? colred_workspace_bytes(rows, C) : 32; }
+static size_t bias_grad_ws(size_t rows, int C) { return C % 4 == 0 || C > 4 ? colred_workspace_bytes(rows, C) : 32; }
+
+// Dense layers whose width is not one the matrix-core kernels take (in % 4 or out % 4, beyond the small-output heads): one fp32 GEMM
+// C[m, n] = act(sum_k A(m, k) B(k, n) + bias[n]) with A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn], so the forward, the data gradient
+// (B = w read transposed) and the weight gradient (A = x read transposed) are the same kernel.  16 x 16 output tiles through LDS; each output is one
+// fmaf chain in k order (the zero padding of the last k tile adds exact zeros), so results do not depend on the launch.
+__global__ __launch_bounds__(256) void dense_any_kernel(const float* __restrict__ A, const float* __restrict__ Bm, const float* __restrict__ bias,
+                                                        float* __restrict__ C, int M, int N, int K, size_t sam, size_t sak, size_t sbk, size_t sbn, int act,
+                                                        float p) {
+  __shared__ float As[16][17], Bs[16][17];
+  const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+  const int m = blockIdx.y * 16 + ty, n = blockIdx.x * 16 + tx;
+  float acc = 0.f;
+  for (int k0 = 0; k0 < K; k0 += 16) {
+    const int ka = k0 + tx, kb = k0 + ty;
+    As[ty][tx] = (m < M && ka < K) ? A[(size_t)m * sam + (size_t)ka * sak] : 0.f;
+    Bs[ty][tx] = (kb < K && n < N) ? Bm[(size_t)kb * sbk + (size_t)n * sbn] : 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) acc = fmaf(As[ty][kk], Bs[kk][tx], acc);
+    __syncthreads();
+  }
+  if (m < M && n < N) C[(size_t)m * N + n] = act_apply(bias ? acc + bias[n] : acc, act, p);
+}
+static int dense_any_gemm(const float* A, const float* Bm, const float* bias, float* C, int M, int N, int K, size_t sam, size_t sak, size_t sbk, size_t sbn,
+                          int act, float p, hipStream_t s) {
+  if (M <= 0 || N <= 0) return GN_OK;
+  if ((M + 15) / 16 > 65535) { set_error("dense: %d rows exceed the grid", M); return GN_EINVAL; }
+  hipLaunchKernelGGL(dense_any_kernel, dim3(cdiv(N, 16), cdiv(M, 16)), dim3(256), 0, s, A, Bm, bias, C, M, N, K, sam, sak, sbk, sbn, act, p);
+  return check_launch("dense_any");
+}
+static bool dense_any_shape(int in, int out) { return (in % 4 || out % 4) && !(out <= 4 && in % 4 == 0); }
 
 }  // namespace gn
 
@@ -503,15 +534,25 @@ int gn_conv1d_up2_unfold_grad(const float* dwf, const float* dbf, float* dw, flo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+size_t gn_bias_grad_workspace(size_t rows, int C) { return bias_grad_ws(rows, C) + 256; }
+
+int gn_bias_grad(const float* dy, float* db, void* ws, size_t ws_bytes, size_t rows, int C, void* stream) {
+  GN_REQUIRE(dy && db && ws && rows > 0 && C > 0, "bias_grad: bad arguments");
+  return bias_grad(dy, db, rows, C, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int gn_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B, int in, int out, int act, float act_param, void* stream) {
   GN_REQUIRE(x && w && y && B >= 0 && in > 0 && out > 0, "dense_fwd: bad arguments");
   if (B == 0) return GN_OK;
+  if (dense_any_shape(in, out))
+    return dense_any_gemm(x, w, bias, y, B, out, in, (size_t)in, 1, (size_t)out, 1, act, act_param, (hipStream_t)stream);
   if (out <= 4) return dense_small_fwd(x, w, bias, y, B, in, out, act, act_param, (hipStream_t)stream);
   return conv_mfma_dispatch(fwd_args(x, w, bias, y, 1, B, in, out, 1, 1, 0, B, act, act_param), (hipStream_t)stream);
 }
 
 size_t gn_dense_bwd_workspace(int B, int in, int out) {
   if (out <= 4) return 256;
+  if (dense_any_shape(in, out)) return bias_grad_ws((size_t)B, out) + 256;
   size_t w = wgrad_workspace_bytes(1, B, in, out, 1);
   size_t b = bias_grad_ws((size_t)B, out);
   return (w > b ? w : b) + (size_t)in * out * sizeof(float) + 256;
@@ -527,6 +568,14 @@ int gn_dense_bwd_fused(const float* x, const float* w, const float* dy, float* d
 int gn_dense_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, void* ws, size_t ws_bytes, int B, int in, int out, void* stream) {
   GN_REQUIRE(x && w && dy && dw && B > 0 && in > 0 && out > 0, "dense_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
+  if (dense_any_shape(in, out)) {
+    // dx = dy w^T, dw = x^T dy, db = column sums of dy (bias_grad: fixed order for out > 4)
+    GN_REQUIRE(ws && ws_bytes >= bias_grad_ws((size_t)B, out), "dense_bwd: workspace too small");
+    int rc = dx ? dense_any_gemm(dy, w, nullptr, dx, B, in, out, (size_t)out, 1, 1, (size_t)out, GN_ACT_LINEAR, 0.f, s) : GN_OK;
+    if (!rc) rc = dense_any_gemm(x, dy, nullptr, dw, in, out, B, 1, (size_t)in, (size_t)out, 1, GN_ACT_LINEAR, 0.f, s);
+    if (!rc && db) rc = bias_grad(dy, db, (size_t)B, out, ws, ws_bytes, s);
+    return rc;
+  }
   if (out <= 4) return dense_small_bwd(x, w, dy, dx, dw, db, B, in, out, s);
   GN_REQUIRE(ws && ws_bytes >= gn_dense_bwd_workspace(B, in, out), "dense_bwd: workspace too small");
   const size_t wt_bytes = (size_t)in * out * sizeof(float);

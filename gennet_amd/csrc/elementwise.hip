@@ -494,6 +494,60 @@ __global__ __launch_bounds__(256) void colred_kernel(ColRedArgs a) {
   }
 }
 
+// C % 4 != 0: the same reduction with a thread on ONE column (scalar loads) x one row lane; grid = (column blocks, row chunks), partials
+// [chunk][NV][C] as above, so colred_final_kernel sums them in the same fixed order.  (No on-the-fly conv gradient here: lazy_dy_check
+// requires C % 4 == 0.)
+template <int MODE>
+__global__ __launch_bounds__(256) void colred_anyc_kernel(ColRedArgs a) {
+  constexpr int NV = MODE == 0 ? 1 : 2;
+  const int NCc = a.C < 256 ? a.C : 256;
+  const int RL = 256 / NCc;
+  const int tid = threadIdx.x, cl = tid % NCc, rl = tid / NCc;
+  const int c = blockIdx.x * NCc + cl;
+  double s[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = 0.0;
+  const size_t r_lo = (size_t)blockIdx.y * a.rows_per_chunk;
+  const size_t r_hi = r_lo + a.rows_per_chunk < a.rows ? r_lo + a.rows_per_chunk : a.rows;
+  if (rl < RL && c < a.C) {
+    float mu = 0.f, is = 0.f, sc = 0.f, sh = 0.f;
+    if (MODE == 2) {
+      mu = a.mean[c]; is = a.invstd[c];
+      if (a.scale) { sc = a.scale[c]; sh = a.shift[c]; }
+    }
+    for (size_t r = r_lo + rl; r < r_hi; r += RL) {
+      const size_t o = r * a.C + c;
+      const float v = a.a[o];
+      if (MODE == 0) {
+        s[0] += (double)v;
+      } else if (MODE == 1) {
+        s[0] += (double)v;
+        s[NV - 1] += (double)v * (double)v;
+      } else {
+        const float xv = a.xpre[o];
+        const uint8_t k = a.mask ? a.mask[o] : (uint8_t)1;
+        const float g = a.scale ? bn_bwd_g_act(v, act_apply(fmaf(xv, sc, sh), a.act, a.act_param), k, a.act, a.act_param, a.keep_scale)
+                                : bn_bwd_g(v, a.y[o], k, a.act, a.act_param, a.keep_scale);
+        const float xh = (xv - mu) * is;
+        s[0] += (double)g;
+        s[NV - 1] += (double)g * (double)xh;
+      }
+    }
+  }
+  __shared__ double red[256];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    red[tid] = s[v];
+    __syncthreads();
+    if (rl == 0 && c < a.C) {
+      double t = red[cl];
+      for (int k = 1; k < RL; ++k) t += red[k * NCc + cl];
+      a.part[((size_t)blockIdx.y * NV + v) * a.C + c] = t;
+    }
+    __syncthreads();
+  }
+}
+
 // sum the chunk partials: block = 32 columns x 8 chunk lanes; lane l adds chunks l, l+8, ... then the 8 lane sums are added in
 // lane order (fixed order -> bitwise reproducible)
 template <typename OUT, int COLS>
@@ -522,6 +576,14 @@ static void colred_final_launch(const double* part, OUT* out, size_t n, int chun
 }
 
 static int colred_chunks(size_t rows, int C) {
+  if (C % 4) {                                          // colred_anyc_kernel: one column per thread, RL rows per block
+    const int NCc = C < 256 ? C : 256, RL = 256 / NCc;
+    const int gx = (C + NCc - 1) / NCc;
+    int chunks = (1024 + gx - 1) / gx;
+    const size_t max_chunks = (rows + (size_t)RL * 4 - 1) / ((size_t)RL * 4);
+    if ((size_t)chunks > max_chunks) chunks = (int)max_chunks;
+    return chunks < 1 ? 1 : chunks;
+  }
   const int NQ = C / 4, NQc = NQ < 256 ? NQ : 256, RL = 256 / NQc;
   const int gx = (NQ + NQc - 1) / NQc;
   int chunks = (1024 + gx - 1) / gx;
@@ -534,18 +596,27 @@ size_t colred_workspace_bytes(size_t rows, int C) { return (size_t)colred_chunks
 
 // out_f64 (NV*C doubles) or out_f32 (MODE 0 only) receives the reduced sums
 int colred_run(int mode, ColRedArgs a, void* ws, size_t ws_bytes, double* out_f64, float* out_f32, hipStream_t s) {
-  if (a.C % 4) { set_error("column reduction: C %d %% 4 != 0", a.C); return GN_EINVAL; }
+  if (a.C < 1) { set_error("column reduction: C %d", a.C); return GN_EINVAL; }
+  if (a.C % 4 && a.lz.g) { set_error("column reduction: the on-the-fly conv gradient needs C %% 4 == 0"); return GN_EINVAL; }
   if (a.rows == 0) { set_error("column reduction: no rows"); return GN_EINVAL; }
   const int chunks = colred_chunks(a.rows, a.C);
   const int NV = mode == 0 ? 1 : 2;
   if (ws_bytes < (size_t)chunks * NV * a.C * sizeof(double)) { set_error("column reduction: workspace too small"); return GN_EWORKSPACE; }
   a.part = (double*)ws;
   a.rows_per_chunk = (int)((a.rows + chunks - 1) / chunks);
-  const int NQ = a.C / 4, NQc = NQ < 256 ? NQ : 256;
-  dim3 grid((NQ + NQc - 1) / NQc, chunks);
-  if (mode == 0) hipLaunchKernelGGL(colred_kernel<0>, grid, dim3(256), 0, s, a);
-  else if (mode == 1) hipLaunchKernelGGL(colred_kernel<1>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(colred_kernel<2>, grid, dim3(256), 0, s, a);
+  if (a.C % 4) {
+    const int NCc = a.C < 256 ? a.C : 256;
+    dim3 grid((a.C + NCc - 1) / NCc, chunks);
+    if (mode == 0) hipLaunchKernelGGL(colred_anyc_kernel<0>, grid, dim3(256), 0, s, a);
+    else if (mode == 1) hipLaunchKernelGGL(colred_anyc_kernel<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(colred_anyc_kernel<2>, grid, dim3(256), 0, s, a);
+  } else {
+    const int NQ = a.C / 4, NQc = NQ < 256 ? NQ : 256;
+    dim3 grid((NQ + NQc - 1) / NQc, chunks);
+    if (mode == 0) hipLaunchKernelGGL(colred_kernel<0>, grid, dim3(256), 0, s, a);
+    else if (mode == 1) hipLaunchKernelGGL(colred_kernel<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(colred_kernel<2>, grid, dim3(256), 0, s, a);
+  }
   int rc = check_launch("colred");
   if (rc) return rc;
   const size_t n = (size_t)NV * a.C;
@@ -642,8 +713,24 @@ __global__ void bn_apply_kernel(const float4* __restrict__ x, const float4* __re
     y[i] = o;
   }
 }
+// C % 4 != 0: one element per thread, the same arithmetic
+__global__ void bn_apply_anyc_kernel(const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
+                                     const uint8_t* __restrict__ mask, float* __restrict__ y, size_t n, int C, int act, float p, float keep_scale) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int c = (int)(i % C);
+    float o = act_apply(fmaf(x[i], scale[c], shift[c]), act, p);
+    if (mask) o = mask[i] ? o * keep_scale : 0.f;
+    y[i] = o;
+  }
+}
 int bn_apply(const float* x, const float* scale, const float* shift, const uint8_t* mask, float* y, size_t rows, int C, int act, float p, float rate, hipStream_t s) {
-  if (C % 4) { set_error("bn_apply: C %d %% 4 != 0", C); return GN_EINVAL; }
+  if (C % 4) {
+    const size_t n = rows * C;
+    if (!n) return GN_OK;
+    hipLaunchKernelGGL(bn_apply_anyc_kernel, dim3(stream_grid(n)), dim3(256), 0, s, x, scale, shift, mask, y, n, C, act, p, 1.0f / (1.0f - rate));
+    return check_launch("bn_apply");
+  }
   const size_t n4 = rows * (C / 4);
   if (!n4) return GN_OK;
   hipLaunchKernelGGL(bn_apply_kernel, dim3(stream_grid(n4)), dim3(256), 0, s, (const float4*)x, (const float4*)scale, (const float4*)shift,
@@ -653,11 +740,14 @@ int bn_apply(const float* x, const float* scale, const float* shift, const uint8
 
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x, const uint8_t* __restrict__ mask,
                                     const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ invstd,
-                                    const double* __restrict__ dsums, double count, float* __restrict__ dx, size_t n, int C, int act, float p, float keep_scale) {
+                                    const double* __restrict__ dsums, double count, float* __restrict__ dx, size_t n, int C, int act, float p, float keep_scale,
+                                    const float* __restrict__ scale, const float* __restrict__ shift) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int c = (int)(i % C);
-    const float g = bn_bwd_g(dy[i], y[i], mask ? mask[i] : (uint8_t)1, act, p, keep_scale);
+    const uint8_t keep = mask ? mask[i] : (uint8_t)1;
+    const float g = scale ? bn_bwd_g_act(dy[i], act_apply(fmaf(x[i], scale[c], shift[c]), act, p), keep, act, p, keep_scale)   // as the v4 kernel
+                          : bn_bwd_g(dy[i], y[i], keep, act, p, keep_scale);
     const float inv = invstd[c];
     const float xh = (x[i] - mean[c]) * inv;
     const float mg = (float)(dsums[c] / count), mgx = (float)(dsums[C + c] / count);
@@ -766,9 +856,9 @@ int bn_bwd_apply(const float* dy, const float* y, const float* x, const uint8_t*
     hipLaunchKernelGGL(bn_bwd_apply_v4_kernel, dim3((unsigned)(chunks * qblocks)), dim3(256), 0, s, dy, y, x, mask, gamma, mean, invstd, dsums_global, count, scale,
                        shift, dx, rows, C, (int)rpc, act, p, 1.0f / (1.0f - rate), z);
   } else {
-    if (!y) { set_error("bn_bwd_apply: C %d %% 4 != 0 needs the stored layer output y", C); return GN_EINVAL; }
+    if (!y && !scale) { set_error("bn_bwd_apply: C %d %% 4 != 0 needs the stored layer output y or scale / shift", C); return GN_EINVAL; }
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n)), dim3(256), 0, s, dy, y, x, mask, gamma, mean, invstd, dsums_global, count, dx, n, C, act, p,
-                       1.0f / (1.0f - rate));
+                       1.0f / (1.0f - rate), y ? nullptr : scale, y ? nullptr : shift);     // a stored output is read as before
   }
   int rc = check_launch("bn_bwd_apply");
   if (rc) return rc;

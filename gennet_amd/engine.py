@@ -1091,7 +1091,7 @@ class Model(Layer):
         n_out = len(self.output_ids)
         ys = list(y) if (isinstance(y, (list, tuple)) and n_out > 1) else [y]
         assert len(ys) == n_out, 'model has %d outputs' % n_out
-        return [to_device(a).reshape(B, 1) for a in ys]
+        return [to_device(a).reshape(B, -1) for a in ys]
 
     def train_on_batch(self, x, y, dropout_masks=None, capture=None, row_map=None):
         """One optimizer step.  Returns [loss, (per-output losses,) (accuracies)] as python floats, keras order.
@@ -1123,7 +1123,10 @@ class Model(Layer):
         outs = self._forward(xs, ctx)
         dps, stats = [], []
         for p, t, kind, scale in zip(outs, ys, self._losses, self._loss_scales):
-            d, o = ops.loss(kind, p.reshape(B, 1), t, B * world)
+            # keras: the loss is the mean over the output's columns, then over the batch -- the element-wise kernel over all B * n values,
+            # normalised by the global element count (n = 1: the (B, 1) heads as before)
+            n = p.numel() // B if B else 1
+            d, o = ops.loss(kind, p.reshape(B * n, 1), t.reshape(B * n, 1), B * world * n)
             if scale != 1.0:
                 ops.axpy(d, d.clone(), scale - 1.0)
             dps.append(d.reshape(p.shape)); stats.append(o)
@@ -1147,7 +1150,8 @@ class Model(Layer):
         if len(losses) > 1:
             res += losses
         if self.metrics:
-            res += [float(h) / (B * world) for h in st[:, 1]]
+            cols = [int(np.prod(self.nodes[i].out_shape)) for i in self.output_ids]
+            res += [float(h) / (B * world * n) for h, n in zip(st[:, 1], cols)]
         return res
 
     def predict_device(self, x, batch_size=32):

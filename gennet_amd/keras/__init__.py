@@ -4,7 +4,7 @@
     from gennet_amd.keras.layers import Dense, Input, Reshape, Dropout
     from gennet_amd.keras.layers.core import Activation, Flatten
     from gennet_amd.keras.layers.normalization import BatchNormalization
-    from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D
+    from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.engine.topology import Layer
@@ -42,8 +42,8 @@ def _pick(mod, *names):
 
 _core = _pick(_layers, 'Activation', 'Dense', 'Dropout', 'Flatten', 'Reshape')
 _norm = _pick(_layers, 'BatchNormalization')
-_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'UpSampling1D', 'MaxPooling2D'),
-             **_unused('37-38', 'UpSampling2D', 'Conv2DTranspose', 'AveragePooling1D', 'MaxPooling1D'))
+_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'UpSampling1D', 'MaxPooling2D'),
+             **_unused('37-38', 'UpSampling2D', 'AveragePooling1D', 'MaxPooling1D'))
 _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU'), **_unused('39', 'ThresholdedReLU'))
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))

@@ -184,6 +184,10 @@ def layer_config(layer):
     elif isinstance(layer, L.Conv1D):
         cfg.update(filters=layer.filters, kernel_size=[layer.k], strides=[layer.stride], padding=layer.padding, data_format='channels_last',
                    dilation_rate=[1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+    elif isinstance(layer, L.Conv2DTranspose):
+        # the keys (and values) keras 2.1.6 wrote for the reference's g_model.hdf5: no dilation_rate / output_padding
+        cfg.update(filters=layer.filters, kernel_size=[1, layer.k], strides=[1, layer.stride], padding=layer.padding, data_format='channels_last',
+                   activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
     elif isinstance(layer, L.Conv2D):
         cfg.update(filters=layer.filters, kernel_size=[layer.kh, layer.kw], strides=[layer.sh, layer.sw], padding=layer.padding,
                    data_format='channels_last', dilation_rate=[1, 1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
@@ -281,6 +285,13 @@ def _layer_from_config(class_name, cfg, custom_objects):
         init_ok(cfg.get('kernel_initializer'))
         return L.Conv2D(cfg['filters'], tuple(cfg['kernel_size']), strides=tuple(cfg.get('strides', (1, 1))), padding=cfg.get('padding', 'valid'),
                         activation=cfg.get('activation'), use_bias=cfg.get('use_bias', True), **kw)
+    if class_name == 'Conv2DTranspose':
+        init_ok(cfg.get('kernel_initializer'))
+        dil = cfg.get('dilation_rate', [1, 1])
+        return L.Conv2DTranspose(cfg['filters'], tuple(cfg['kernel_size']), strides=tuple(cfg.get('strides', (1, 1))), padding=cfg.get('padding', 'valid'),
+                                 output_padding=cfg.get('output_padding'), data_format=cfg.get('data_format'),
+                                 dilation_rate=tuple(dil) if isinstance(dil, (list, tuple)) else dil, activation=cfg.get('activation'),
+                                 use_bias=cfg.get('use_bias', True), **kw)
     if class_name == 'BatchNormalization':
         return L.BatchNormalization(axis=cfg.get('axis', -1), momentum=cfg.get('momentum', 0.99), epsilon=cfg.get('epsilon', 1e-3), **kw)
     if class_name == 'PReLU':

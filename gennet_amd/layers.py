@@ -53,7 +53,8 @@ class Dense(Layer):
 
     @property
     def can_absorb_prev_act_bwd(self):
-        return self.units <= 4
+        k = getattr(self, 'kernel', None)          # the fused small-output backward needs an input width that is a multiple of 4
+        return self.units <= 4 and (k is None or k.shape[0] % 4 == 0)
 
     def __init__(self, units, activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
         Layer.__init__(self, **kw)
@@ -298,6 +299,125 @@ class Conv2D(Layer):
         return None
 
 
+def _pair(v, what):
+    t = (v, v) if isinstance(v, int) else tuple(int(u) for u in v)
+    if len(t) != 2:
+        raise ValueError('Conv2DTranspose: %s %r is not a pair' % (what, v))
+    return t
+
+
+class Conv2DTranspose(Layer):
+    """keras.layers.Conv2DTranspose (keras 2.2.4, channels_last) with kernel (1, kw) and strides (1, s), s in {1, 2}: the layer of the reference's
+    g_model.hdf5 and of 2_model_version/*/noise_gan.py.  Rows are independent, so (B, H, W, Cin) runs as B*H sequences of length W.
+
+    TF's conv2d_transpose is the gradient, with respect to its input, of a conv2d over the output length with the same padding rule, and the
+    keras kernel (1, kw, filters, Cin) with kh dropped is exactly this project's Conv1D layout (k, Cin=filters, Cout=Cin) of that adjoint conv.
+    So the layer runs on the Conv1D kernel families: forward = the adjoint's data gradient plus the bias / activation / dropout pass of
+    csrc/conv_transpose.hip; data gradient = the adjoint's forward; weight gradient = the adjoint's weight gradient with the operands swapped;
+    more than 5 taps through the tap fold, as Conv1D does."""
+    fusable_act = True
+    fusable_drop = True
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', output_padding=None, data_format=None, dilation_rate=(1, 1),
+                 activation=None, use_bias=True, kernel_initializer='glorot_uniform', **kw):
+        Layer.__init__(self, **kw)
+        _check_init(kernel_initializer)
+        self.filters = int(filters)
+        kh, self.k = _pair(kernel_size, 'kernel_size')
+        sh, self.stride = _pair(strides, 'strides')
+        supported = ('Conv2DTranspose is implemented for kernel (1, kw) with 1 <= kw <= 40, strides (1, 1) or (1, 2), padding "valid" or "same", '
+                     'dilation (1, 1), no output_padding, use_bias=True, channels_last')
+        if kh != 1 or sh != 1 or self.stride not in (1, 2) or not 1 <= self.k <= 40:
+            raise NotImplementedError('%s (got kernel_size %r, strides %r)' % (supported, kernel_size, strides))
+        if _pair(dilation_rate, 'dilation_rate') != (1, 1) or output_padding is not None or not use_bias:
+            raise NotImplementedError('%s (got dilation_rate %r, output_padding %r, use_bias %r)' % (supported, dilation_rate, output_padding, use_bias))
+        if data_format not in (None, 'channels_last'):
+            raise NotImplementedError('%s (got data_format %r)' % (supported, data_format))
+        if padding not in ('same', 'valid'):
+            raise NotImplementedError('%s (got padding %r)' % (supported, padding))
+        if self.k < self.stride:
+            raise NotImplementedError('Conv2DTranspose(kernel (1, %d), strides (1, %d)): every stride phase needs a tap (kw >= s)' % (self.k, self.stride))
+        self.padding = padding
+        self.activation = _ACT_NAMES[activation]
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError('Conv2DTranspose expects (batch, H, W, channels) inputs, got %r' % (tuple(input_shape),))
+        # the adjoint conv's channels (its input: filters, tap-folded to G * filters past 5 taps; its output: Cin) must suit a conv kernel family:
+        # both multiples of 4, or one side <= 4 and the other a multiple of 4
+        a, b = ops.tap_groups(self.k)[0] * self.filters if self.k > 5 else self.filters, input_shape[2]
+        if not ((a % 4 == 0 and b % 4 == 0) or (a <= 4 and b % 4 == 0) or (b <= 4 and a % 4 == 0)):
+            raise NotImplementedError('Conv2DTranspose(%d filters, kernel (1, %d)) on %d input channels: the conv kernels need both channel counts '
+                                      'multiples of 4, or one of them <= 4 and the other a multiple of 4' % (self.filters, self.k, input_shape[2]))
+        # keras' layout (1, kw, filters, Cin): glorot limit sqrt(6 / ((filters + Cin) kw)), and .h5 reads / writes are plain copies
+        self.kernel = self.add_weight('kernel', glorot_uniform((1, self.k, self.filters, input_shape[2])))
+        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
+
+    def out_length(self, W):
+        """keras deconv_length (conv_utils.py) for 'valid' / 'same' without output_padding."""
+        return W * self.stride + max(self.k - self.stride, 0) if self.padding == 'valid' else W * self.stride
+
+    def compute_output_shape(self, input_shape):
+        return (input_shape[0], self.out_length(input_shape[1]), self.filters)
+
+    def _pad_left(self, Wout):
+        return ops.conv_geometry(Wout, self.k, self.stride, self.padding)[1]
+
+    def _act(self, node):
+        if node.fused_act is not None and self.activation[0] != 'linear':
+            raise NotImplementedError('Conv2DTranspose(activation=...) followed by another activation layer')
+        return node.fused_act or self.activation
+
+    def forward(self, ctx, node, x):
+        a = self._act(node)
+        B, H, W, Cin = x.shape
+        Wout = self.out_length(W)
+        pl = self._pad_left(Wout)
+        x3 = x.contiguous().view(B * H, W, Cin)
+        wadj = self.kernel.data.view(self.k, self.filters, Cin)         # the adjoint Conv1D's kernel (k, Cin=filters, Cout=Cin), no copy
+        if self.k > 5:
+            w2 = ops.conv1d_tapfold_w(wadj)
+            y = ops.conv1d_tapunfold_dx(ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(w2), Wout + pl, self.stride, 0), Wout, self.k, pl)
+        else:
+            y = ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(wadj), Wout, self.stride, pl)
+        mask, rate = None, 0.0
+        if ctx.training and node.fused_drop is not None and node.fused_drop[0] > 0.0:
+            rate, drop_layer = node.fused_drop
+            if ctx.dropout_masks.get(drop_layer.name) is None and ctx.row_map is None:
+                mask = torch.empty(y.shape, dtype=torch.uint8, device=y.device)
+                ops.bias_act_dropout(y, self.bias.data, a[0], a[1], mask, rate, gen=device_rng().take(y.numel()))
+            else:                          # injected mask, or data parallelism: Dropout's own draw over the layer's (B, H, Wout, filters) shape
+                mask = drop_layer.make_mask(ctx, (B, H, Wout, self.filters)).view(y.shape)
+                ops.bias_act_dropout(y, self.bias.data, a[0], a[1], mask, rate)
+        else:
+            ops.bias_act_dropout(y, self.bias.data, a[0], a[1])
+        ctx.tape[node.index] = (x3, y, a, pl, mask, rate, (B, H, W, Cin))
+        y = y.view(B, H, Wout, self.filters)
+        if ctx.training and (a[0] != 'linear' or mask is not None):
+            ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
+        return y
+
+    def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
+        x3, y, a, pl, mask, rate, xshape = ctx.tape.pop(node.index)
+        dy = _conv_bwd_epilogue(dy.contiguous().view(y.shape), y, a, mask, rate, ctx, node)      # (B*H, Wout, filters)
+        W = x3.shape[1]
+        wadj = self.kernel.data.view(self.k, self.filters, x3.shape[2])
+        if need_dw:
+            ops.bias_grad(dy.view(-1, self.filters), self.bias.grad)
+            if self.k > 5:
+                dw2, _ = ops.conv1d_wgrad(ops.conv1d_tapfold_x(dy, self.k, pl), x3, ops.tap_groups(self.k)[1], self.stride, 0, want_db=False)
+                ops.conv1d_tapunfold_dw(dw2, self.k, self.kernel.grad.view(wadj.shape))
+            else:
+                ops.conv1d_wgrad(dy, x3, self.k, self.stride, pl, self.kernel.grad.view(wadj.shape), want_db=False)   # the adjoint's bias: none
+        if not need_dx:
+            return None
+        if self.k > 5:
+            dx = ops.conv1d_fwd(ops.conv1d_tapfold_x(dy, self.k, pl), ops.conv1d_tapfold_w(wadj), None, self.stride, 0, W)
+        else:
+            dx = ops.conv1d_fwd(dy, wadj, None, self.stride, pl, W)
+        return dx.view(xshape)
+
+
 BN_MOVING_AVERAGE = 'tf_zero_debias'       # default form of the moving-statistics update (BatchNormalization docstring)
 
 
@@ -401,9 +521,7 @@ class BatchNormalization(Layer):
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
         x2, mask, smean, sinv, count, act, rate, scale, shift = ctx.tape.pop(node.index)
-        y = None
-        if x2.shape[1] % 4:            # the scalar fallback kernels read the stored output; not reached by the BBH nets
-            raise NotImplementedError('BatchNormalization backward over %d channels (not a multiple of 4)' % x2.shape[1])
+        y = None                       # any channel count: the activation output is recomputed from x2 with scale / shift
         lazy = isinstance(dy, ops.ConvGrad1)
         if lazy:
             local = ops.bn_bwd_stats_conv1(dy, x2, mask, smean, sinv, act[0], act[1], rate, scale, shift)

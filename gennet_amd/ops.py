@@ -164,18 +164,43 @@ def can_fuse_dgrad(Cin, Cout):
     return Cin > 4 and Cout > 4
 
 
-def conv1d_wgrad(x, dy, k, stride, pad_left, dw=None, db=None):
+def conv1d_wgrad(x, dy, k, stride, pad_left, dw=None, db=None, want_db=True):
+    """want_db=False: no bias gradient at all (db stays None; the kernels are handed NULL and skip the column sum of dy)."""
     _chk(x, dy, dw, db)
     B, L, Cin = x.shape
     _, Lout, Cout = dy.shape
     if dw is None:
         dw = torch.empty((k, Cin, Cout), dtype=torch.float32, device=x.device)
-    if db is None:
+    if db is None and want_db:
         db = torch.empty((Cout,), dtype=torch.float32, device=x.device)
     nb = _lib.size('gn_conv1d_wgrad_workspace', B, L, Cin, Cout, k, stride, Lout)
     ws = workspace(nb, x.device)
     _lib.call('gn_conv1d_wgrad', _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(), B, L, Cin, Cout, k, stride, pad_left, Lout, _stream())
     return dw, db
+
+
+def bias_act_dropout(y, b, act='linear', act_param=0.0, mask=None, rate=0.0, gen=None):
+    """In place: y = act(y + b) over the last axis, any channel count (csrc/conv_transpose.hip); with mask, inverted dropout after it.
+    gen = (seed, offset): the keep-mask is drawn into `mask` in the same pass (gn_dropout_mask's draw); otherwise `mask` is read."""
+    _chk(y, b, mask)
+    C = y.shape[-1]
+    if mask is not None:
+        assert mask.numel() == y.numel()
+    seed, off = gen if gen is not None else (0, 0)
+    _lib.call('gn_bias_act_dropout', _p(y), _p(b), _p(mask), y.numel() // C, C, ACT[act], float(act_param), float(rate), 1 if gen is not None else 0,
+              int(seed), int(off), _stream())
+    return y
+
+
+def bias_grad(dy2d, db=None):
+    """db[c] = sum over rows of dy2d[row, c] (the bias-gradient reduction of dense_bwd / conv1d_wgrad), any column count."""
+    _chk(dy2d, db)
+    rows, C = dy2d.shape
+    if db is None:
+        db = torch.empty((C,), dtype=torch.float32, device=dy2d.device)
+    ws = workspace(_lib.size('gn_bias_grad_workspace', rows, C), dy2d.device)
+    _lib.call('gn_bias_grad', _p(dy2d), _p(db), _p(ws), ws.numel(), rows, C, _stream())
+    return db
 
 
 def conv2d_w2_fold(w, b):

@@ -137,7 +137,7 @@ int gn_conv1d_up2_unfold_grad(const float* dwf, const float* dbf, float* dw, flo
 
 /* ---- Dense (bbhMahoGANy.py:234 generator 100 -> 256*n_pix/2; :377,:399,:494 flatten -> 1 heads) -------------
  * y[b,o] = act(bias[o] + sum_i x[b,i] * w[i,o]).  Large `out` goes through the MFMA GEMM, out <= 4 through
- * the streaming dot-product kernel. */
+ * the streaming dot-product kernel; widths neither takes (in % 4 or out % 4 nonzero) through one tiled fp32 GEMM kernel. */
 int gn_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B, int in, int out,
                  int act, float act_param, void* stream);
 /* dw[i,o] = sum_b x[b,i]*dy[b,o]; db[o] = sum_b dy[b,o]; dx[b,i] = sum_o dy[b,o]*w[i,o] (dx may be NULL). */
@@ -160,6 +160,15 @@ int gn_act_dropout_bwd(const float* dy, const float* y, const uint8_t* mask, flo
  * mask_out for the backward pass: y = mask ? act(x * scale + shift) / (1 - rate) : 0.  C % 4 == 0. */
 int gn_bn_apply_dropgen(const float* x, const float* scale, const float* shift, uint8_t* mask_out, float* y, size_t rows, int C,
                         int act, float act_param, float rate, uint64_t seed, uint64_t offset, void* stream);
+/* Conv2DTranspose epilogue (csrc/conv_transpose.hip), in place over the (rows, C) output of the adjoint conv's data gradient, any C:
+ * y = act(y + bias[c]); with mask, y = keep ? y / (1 - rate) : 0.  gen != 0 draws the keep-mask into mask (4-byte aligned) in the same pass,
+ * the draw of gn_dropout_mask bit for bit; gen == 0 reads mask (NULL: no dropout, rate must be 0). */
+int gn_bias_act_dropout(float* y, const float* bias, uint8_t* mask, size_t rows, int C, int act, float act_param, float rate, int gen,
+                        uint64_t seed, uint64_t offset, void* stream);
+/* db[c] = sum over rows of dy[row, c] (the bias gradient of gn_dense_bwd / gn_conv1d_wgrad), any C: fixed summation order for C > 4 and for
+ * C % 4 == 0; fp64 atomics for C in {1, 2, 3}.  ws: gn_bias_grad_workspace(rows, C) bytes. */
+size_t gn_bias_grad_workspace(size_t rows, int C);
+int gn_bias_grad(const float* dy, float* db, void* ws, size_t ws_bytes, size_t rows, int C, void* stream);
 /* Inference-phase BatchNormalization folded into the preceding convolution (generator.predict, bbhMahoGANy.py:1248, :1330):
  * w_out[r, n] = w[r, n] * scale[n] (r over taps * Cin rows), bias_out[n] = bias[n] * scale[n] + shift[n], with scale / shift
  * from gn_bn_infer_coeffs; conv(x; w_out, bias_out) then equals BN_infer(conv(x; w, bias)).  Cout % 4 == 0; bias may be NULL. */
