@@ -19,6 +19,9 @@ _SIGS = {
     'gn_conv1d_fwd_wino': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     'gn_conv1d_fwd_stats': [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     'gn_conv1d_fwd_dropout': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp],
+    'gn_conv1d_fwd_any': [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    'gn_conv1d_dgrad_any': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    'gn_conv1d_wgrad_any': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     'gn_conv1d_transpose_w': [vp, vp, i32, i32, i32, vp],
     'gn_conv1d_dgrad': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     'gn_conv1d_dgrad_fused': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp],
@@ -114,6 +117,11 @@ _SIZE_FNS = {
 }
 
 
+_PREDICATES = {                       # int-valued queries (0 / 1), no error code
+    'gn_conv1d_needs_any': [i32, i32],
+}
+
+
 class GennetHipError(RuntimeError):
     pass
 
@@ -134,7 +142,7 @@ def lib():
         # already-loaded copy.  Loading in the other order gives the process two HIP runtimes and launches fail.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table, restype in ((_SIGS, i32), (_SIZE_FNS, sz)):
+        for table, restype in ((_SIGS, i32), (_SIZE_FNS, sz), (_PREDICATES, i32)):
             for name, args in table.items():
                 try:
                     fn = getattr(L, name)
@@ -149,7 +157,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGS) + list(_SIZE_FNS) + ['gn_last_error', 'gn_version'])
+    return sorted(list(_SIGS) + list(_SIZE_FNS) + list(_PREDICATES) + ['gn_last_error', 'gn_version'])
 
 
 def call(name, *args):
@@ -165,3 +173,12 @@ def call(name, *args):
 
 def size(name, *args):
     return int(getattr(lib(), name)(*args))
+
+
+def predicate(name, *args):
+    L = lib()
+    try:
+        fn = getattr(L, name)
+    except AttributeError:
+        raise GennetHipError('%s is not exported by %s (stale build?)' % (name, LIB_PATH))
+    return bool(fn(*args))

@@ -93,6 +93,9 @@ const Switches& switches() {
 //   bf16x3   fwd, dgrad, wgrad (1)  Cin, Cout >= 256 and GN_BF16X3_MIN_GFLOP (split_worth_it)          the split operands | wgrad_workspace_bytes
 //   merged   dgrad                  stride 2, 5 taps, few tiles; not bf16x3, NOMERGE, NOPIPE or NODMA   - | -
 //   direct   everything else        conv_mfma_dispatch / wgrad_mfma_dispatch pick tile and member       - | wgrad_workspace_bytes
+//   anyc     fwd, dgrad, wgrad      the _any entry points only (any_channels) and needs_any(Cin, Cout):   - | wgrad_anyc_workspace_bytes
+//            (every math)           the pairs every family above refuses; a strided data gradient
+//                                   runs as phases, each one anyc launch
 static int g_conv_math = 0;
 static void* g_conv_ws = nullptr;
 static size_t g_conv_ws_bytes = 0;
@@ -111,10 +114,21 @@ static bool split_worth_it(const ConvArgs& a, int w_taps) {
   return w_taps > 0 ? split_worth_it(a.B, (a.Ly + 1) / 2, w_taps, a.Cin, a.Cout) : split_worth_it(a.B, a.M, a.t.ntaps, a.Cin, a.Cout);
 }
 
-enum ConvFamily { CONV_SMALL, CONV_WINO, CONV_WINO_S2, CONV_BF16X3, CONV_DIRECT };
+// The channel pairs that end in an error on every family above, read off the dispatchers themselves: Cin <= 4 goes to the small-Cin kernels
+// whatever Cout is, and they need Cout % 4 == 0 (so 4 -> 3 is refused although 3 <= 4); otherwise Cout <= 4 goes to the small-Cout kernels,
+// which need Cin % 4 == 0; everything else needs both counts multiples of 4.  The weight gradient picks its small side the same way.  A data
+// gradient runs the swapped pair, so a layer may need the anyc kernels in one direction only (3 -> 4: forward strict, data gradient 4 -> 3 not).
+// Without the any_channels flag of the _any entry points such pairs still end in that error.
+static bool needs_any(int Cin, int Cout) {
+  const bool strict = Cin <= 4 ? Cout % 4 == 0 : Cout <= 4 ? Cin % 4 == 0 : (Cin % 4 == 0 && Cout % 4 == 0);
+  return !strict;
+}
+
+enum ConvFamily { CONV_SMALL, CONV_WINO, CONV_WINO_S2, CONV_BF16X3, CONV_DIRECT, CONV_ANYC };
 
 // forward, one data-gradient phase, Dense data gradient
 static ConvFamily select_conv(const ConvArgs& a, int w_taps) {
+  if (a.any_channels && needs_any(a.Cin, a.Cout)) return CONV_ANYC;
   if (a.Cin <= 4 || a.Cout <= 4) return CONV_SMALL;
   if (g_conv_math == 2 && a.Cin >= 32 && conv_wino_supported(a) && conv_wino_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return CONV_WINO;
   if (g_conv_math == 2 && conv_wino_s2_kind(a) == 1 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return CONV_WINO_S2;      // stride-2 forward: F(2,3) + F(2,2)
@@ -126,6 +140,7 @@ enum DgradFamily { DGRAD_WINO_S2, DGRAD_BF16X3_MERGED, DGRAD_MERGED, DGRAD_PHASE
 
 // the data gradient of a stride-2, 5-tap layer; a = its merged two-phase form (dgrad_impl).  DGRAD_PHASES: one select_conv launch per phase
 static DgradFamily select_dgrad(const ConvArgs& a) {
+  if (a.any_channels && needs_any(a.Cin, a.Cout)) return DGRAD_PHASES;
   if (a.Ly < 2 || a.Cin <= 4 || a.Cout <= 4) return DGRAD_PHASES;
   if (g_conv_math == 2 && conv_wino_s2_kind(a) == 2 && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return DGRAD_WINO_S2;      // both phases, F(2,3) and F(2,2)
   const Switches& sw = switches();
@@ -136,9 +151,10 @@ static DgradFamily select_dgrad(const ConvArgs& a) {
   return DGRAD_PHASES;
 }
 
-enum WgradFamily { WGRAD_SMALL, WGRAD_WINO, WGRAD_WINO_S2, WGRAD_BF16X3, WGRAD_DIRECT };
+enum WgradFamily { WGRAD_SMALL, WGRAD_WINO, WGRAD_WINO_S2, WGRAD_BF16X3, WGRAD_DIRECT, WGRAD_ANYC };
 
 static WgradFamily select_wgrad(const WgradArgs& a) {
+  if (a.any_channels && needs_any(a.Cin, a.Cout)) return WGRAD_ANYC;
   if (a.Cin <= 4 || a.Cout <= 4) return WGRAD_SMALL;
   if (g_conv_math == 2 && wgrad_wino_supported(a) && conv_wino_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return WGRAD_WINO;
   if (g_conv_math == 2 && wgrad_wino_s2_supported(a) && conv_wino_s2_workspace_bytes(a.Cin, a.Cout) <= kWinoKernelBytes) return WGRAD_WINO_S2;
@@ -149,9 +165,12 @@ static WgradFamily select_wgrad(const WgradArgs& a) {
 // what the weight-gradient family needs of the CALLER's workspace (the bias-gradient pass needs bias_grad_ws on top, not beside)
 static size_t wgrad_ws_need(WgradFamily f, const WgradArgs& a) {
   switch (f) {
-    case WGRAD_SMALL: return wgrad_small_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);
+    // (a pair the small kernels refuse -- reached only without any_channels: its size has no meaning (a large side below 4 divides by zero in
+    //  it) and wgrad_small_dispatch refuses the pair before it looks at the workspace)
+    case WGRAD_SMALL: return needs_any(a.Cin, a.Cout) ? 0 : wgrad_small_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);
     case WGRAD_WINO: return wgrad_wino_workspace_bytes(a.B, a.M, a.Cin, a.Cout);          // six point slabs per split
     case WGRAD_WINO_S2: return wgrad_wino_s2_workspace_bytes(a.B, a.M, a.Cin, a.Cout);    // seven
+    case WGRAD_ANYC: return wgrad_anyc_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);
     default: return wgrad_workspace_bytes(a.B, a.M, a.Cin, a.Cout, a.ntaps);              // direct and bf16x3: the same partial slabs
   }
 }
@@ -185,6 +204,7 @@ static int conv_run(const ConvArgs& a, hipStream_t s, Phases* ph = nullptr) {
         if (ph) ph->have_split = true;
       }
       return conv_bf16x3_run(a, w_taps, g_conv_ws, s);
+    case CONV_ANYC: return conv_anyc_dispatch(a, s);
     default: return conv_mfma_dispatch(a, s);
   }
 }
@@ -330,15 +350,26 @@ int gn_prof_collect(int kind, double* out) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-int gn_conv1d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
-                  int act, float act_param, void* stream) {
+static int fwd_impl(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
+                    int act, float act_param, bool any_channels, void* stream) {
   GN_REQUIRE(x && w && y, "conv1d_fwd: null pointer");
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0, "conv1d_fwd: bad shape");
   GN_REQUIRE(pad_left >= 0 && stride * (Lout - 1) + k - pad_left <= L + k, "conv1d_fwd: Lout %d inconsistent with L %d k %d stride %d", Lout, L, k, stride);
   if (B == 0) return GN_OK;
   ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
+  a.any_channels = any_channels;
   return conv_run(a, (hipStream_t)stream);
 }
+
+int gn_conv1d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
+                  int act, float act_param, void* stream) {
+  return fwd_impl(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param, false, stream);
+}
+int gn_conv1d_fwd_any(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
+                      int act, float act_param, void* stream) {
+  return fwd_impl(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param, true, stream);
+}
+int gn_conv1d_needs_any(int Cin, int Cout) { return needs_any(Cin, Cout) ? 1 : 0; }
 
 int gn_set_conv_math(int mode, void* workspace, size_t workspace_bytes) { return set_conv_math_impl(mode, workspace, workspace_bytes); }
 
@@ -411,7 +442,7 @@ int gn_conv1d_transpose_w(const float* w, float* wt, int k, int Cin, int Cout, v
 }
 
 static int dgrad_impl(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, const float* gy,
-                      const uint8_t* gmask, int gact, float gparam, float grate, void* stream) {
+                      const uint8_t* gmask, int gact, float gparam, float grate, void* stream, bool any_channels = false) {
   GN_REQUIRE(dy && wt && dx, "conv1d_dgrad: null pointer");
   GN_REQUIRE(B >= 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_dgrad: bad shape");
   if (B == 0) return GN_OK;
@@ -424,6 +455,7 @@ static int dgrad_impl(const float* dy, const float* wt, float* dx, int B, int L,
     a.B = B; a.Lin = Lout; a.Cin = Cout; a.Cout = Cin; a.Ly = L;
     a.t.in_stride = 1; a.t.out_stride = stride;
     a.act = GN_ACT_LINEAR;
+    a.any_channels = any_channels;
     a.gy = gy; a.gmask = gmask; a.gact = gact; a.gparam = gparam; a.gscale = 1.0f / (1.0f - grate);
     a.M = (L - std::max(p, 0) + stride - 1) / stride;
     a.t.out_off = p < 0 ? pad_left & 1 : p;                  // merged: the phase of the even taps (kk = 0, 2, 4); the odd ones write out_off_odd
@@ -464,6 +496,10 @@ int gn_conv1d_dgrad(const float* dy, const float* wt, float* dx, int B, int L, i
   return dgrad_impl(dy, wt, dx, B, L, Cin, Cout, k, stride, pad_left, Lout, nullptr, nullptr, GN_ACT_LINEAR, 0.f, 0.f, stream);
 }
 
+int gn_conv1d_dgrad_any(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream) {
+  return dgrad_impl(dy, wt, dx, B, L, Cin, Cout, k, stride, pad_left, Lout, nullptr, nullptr, GN_ACT_LINEAR, 0.f, 0.f, stream, true);
+}
+
 int gn_conv1d_dgrad_fused(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
                           const float* y_prev, const uint8_t* mask_prev, int act_prev, float act_param_prev, float rate_prev, void* stream) {
   GN_REQUIRE(y_prev, "conv1d_dgrad_fused: y_prev is NULL");
@@ -481,17 +517,19 @@ static WgradArgs wgrad_args(const float* x, const float* dy, void* ws, int B, in
 }
 
 size_t gn_conv1d_wgrad_workspace(int B, int L, int Cin, int Cout, int k, int stride, int Lout) {
-  const WgradArgs a = wgrad_args(nullptr, nullptr, nullptr, B, L, Cin, Cout, k, stride, 0, Lout);      // (the need does not depend on pad_left)
+  WgradArgs a = wgrad_args(nullptr, nullptr, nullptr, B, L, Cin, Cout, k, stride, 0, Lout);      // (the need does not depend on pad_left)
+  a.any_channels = 1;       // a pair only gn_conv1d_wgrad_any takes gets that kernel's size; the flag changes nothing for every other pair
   return std::max(wgrad_ws_need(select_wgrad(a), a), bias_grad_ws((size_t)B * Lout, Cout)) + 256;
 }
 
-int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes, int B, int L, int Cin, int Cout, int k, int stride,
-                    int pad_left, int Lout, void* stream) {
+static int wgrad_impl(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes, int B, int L, int Cin, int Cout, int k, int stride,
+                      int pad_left, int Lout, bool any_channels, void* stream) {
   GN_REQUIRE(x && dy && dw && ws, "conv1d_wgrad: null pointer");
   GN_REQUIRE(B > 0 && L > 0 && Cin > 0 && Cout > 0 && k >= 1 && k <= 5 && stride >= 1 && Lout > 0 && pad_left >= 0, "conv1d_wgrad: bad shape");
   hipStream_t s = (hipStream_t)stream;
   WgradArgs a = wgrad_args(x, dy, ws, B, L, Cin, Cout, k, stride, pad_left, Lout);
   a.db = db;
+  a.any_channels = any_channels;
   const WgradFamily f = select_wgrad(a);
   int rc = ws_check("conv1d_wgrad", wgrad_ws_need(f, a), ws_bytes);
   if (rc) return rc;
@@ -504,6 +542,7 @@ int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void*
     }
     case WGRAD_WINO: rc = wgrad_wino_run(a, dw, s); break;           // transform domain; the bias gradient takes the separate pass below
     case WGRAD_WINO_S2: rc = wgrad_wino_s2_run(a, dw, s); break;
+    case WGRAD_ANYC: rc = wgrad_anyc_dispatch(a, dw, ws_bytes, s); break;
     case WGRAD_BF16X3:
       rc = ws_check("conv-math", wgrad_bf16x3_workspace_bytes(B, Lout, Cin, Cout, stride), g_conv_ws_bytes);
       if (!rc) rc = wgrad_bf16x3_dispatch(a, dw, g_conv_ws, g_conv_ws_bytes, s);
@@ -514,6 +553,15 @@ int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void*
   }
   if (rc) return rc;
   return db ? bias_grad(dy, db, (size_t)B * Lout, Cout, ws, ws_bytes, s) : GN_OK;
+}
+
+int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes, int B, int L, int Cin, int Cout, int k, int stride,
+                    int pad_left, int Lout, void* stream) {
+  return wgrad_impl(x, dy, dw, db, ws, ws_bytes, B, L, Cin, Cout, k, stride, pad_left, Lout, false, stream);
+}
+int gn_conv1d_wgrad_any(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes, int B, int L, int Cin, int Cout, int k, int stride,
+                        int pad_left, int Lout, void* stream) {
+  return wgrad_impl(x, dy, dw, db, ws, ws_bytes, B, L, Cin, Cout, k, stride, pad_left, Lout, true, stream);
 }
 
 int gn_conv2d_w2_fold(const float* w, const float* bias, float* wf, float* biasf, int kh, int Cin, int Cout, void* stream) {

@@ -35,7 +35,7 @@ const Switches& switches();
 // rng_base() = the device word every Philox kernel adds to its counter offset (NULL outside graph capture; gn_set_rng_base).
 const uint64_t* rng_base();
 void prof_begin(hipStream_t s);
-void prof_end(hipStream_t s, double flop, int kind, double bytes = 0.0);  // kind 0: conv_mfma (fwd, dgrad), 1: wgrad_mfma, 2: bf16x3 conv, 3: fused synthesiser, 4: fused noise chain, 5: transform-domain conv F(2,5) (flop = executed = 0.6 algorithmic), 6: transform-domain wgrad, 7: transform-domain stride-2 conv (0.7), 8: transform-domain stride-2 wgrad (0.7)
+void prof_end(hipStream_t s, double flop, int kind, double bytes = 0.0);  // kind 0: conv_mfma (fwd, dgrad), 1: wgrad_mfma, 2: bf16x3 conv, 3: fused synthesiser, 4: fused noise chain, 5: transform-domain conv F(2,5) (flop = executed = 0.6 algorithmic), 6: transform-domain wgrad, 7: transform-domain stride-2 conv (0.7), 8: transform-domain stride-2 wgrad (0.7), 9: anyc conv (forward, data gradient, each phase of a strided one), 10: anyc wgrad
 
 
 // ---------------------------------------------------------------------------------------------
@@ -65,6 +65,7 @@ struct ConvArgs {
   ConvTaps t;
   int act;
   float act_param;
+  int any_channels;     // set by the gn_conv1d_*_any entry points only: a channel pair no other family takes runs on the anyc kernels (select_conv)
   const uint8_t* mask;  // optional dropout keep-mask, same shape as y: y = mask ? act(.) * keep_scale : 0 (fused Dropout)
   float keep_scale;
   // gradient epilogue (data-gradient launches): out *= d act(prev)/d pre-activation, expressed through the PRODUCER layer's output
@@ -92,6 +93,7 @@ struct WgradArgs {
   double* db_part;  // optional [splits][Cout]: per-split column sums of dy (the bias gradient), written by the blocks of Cin-tile 0
   float* db;        // optional: where wgrad_mfma_dispatch puts the bias gradient when the kernel it selects can sum it on the way
   int db_done;      // set by the dispatcher when db has been written
+  int any_channels; // set by gn_conv1d_wgrad_any (and the workspace query) only: see ConvArgs
 };
 
 struct WgradSmallArgs {
@@ -169,6 +171,10 @@ int wgrad_wino_s2_run(WgradArgs& a, float* dw, hipStream_t s);
 size_t wgrad_bf16x3_workspace_bytes(int B, int M, int Cin, int Cout, int in_stride);
 bool wgrad_bf16x3_supported(const WgradArgs& a);
 int wgrad_bf16x3_run(const WgradArgs& a, int splits, void* ws, size_t ws_bytes, hipStream_t s);
+// conv_anyc.hip (channel pairs no other family takes; scalar guarded staging, exact fp32 MFMA)
+int conv_anyc_dispatch(const ConvArgs& a, hipStream_t s);
+size_t wgrad_anyc_workspace_bytes(int B, int M, int Cin, int Cout, int ntaps);
+int wgrad_anyc_dispatch(WgradArgs& a, float* dw, size_t ws_bytes, hipStream_t s);
 // small_conv.hip
 int conv_smallcin_dispatch(const ConvArgs& a, hipStream_t s);
 int conv_smallcout_dispatch(const ConvArgs& a, hipStream_t s);

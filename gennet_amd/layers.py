@@ -25,8 +25,11 @@ def _check_init(kernel_initializer):
         raise NotImplementedError('kernel_initializer %r (only glorot_uniform is used on the hot path)' % (kernel_initializer,))
 
 
-def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask):
-    """conv + activation epilogue, plus the following Dropout when the planner fused one (training phase only)."""
+def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any_channels=False):
+    """conv + activation epilogue, plus the following Dropout when the planner fused one (training phase only).  any_channels: the pair needs
+    the `anyc` kernels, which have no fused Dropout (the planner declined it: Conv1D.fusable_drop)."""
+    if any_channels:
+        return ops.conv1d_fwd(x, w, b, stride, pl, Lout, act[0], act[1], any_channels=True), None, 0.0
     if node.fused_drop is not None and ctx.training and node.fused_drop[0] > 0.0:
         rate, drop_layer = node.fused_drop
         mask = drop_layer.make_mask(ctx, out_shape_for_mask)
@@ -102,9 +105,25 @@ class Dense(Layer):
 class Conv1D(Layer):
     """bbhMahoGANy.py:250-292, :362-394."""
     fusable_act = True
-    fusable_drop = True
     offers_act_bwd = True
     can_absorb_prev_act_bwd = True
+
+    def _run_cin(self, Cin):
+        """input channels of the conv that actually runs: the tap fold puts its G tap groups side by side"""
+        return Cin * ops.tap_groups(self.k)[0] if self.k > 5 else Cin
+
+    @property
+    def fusable_drop(self):
+        """The planner (Model._plan) asks per instance: a channel pair that only the `anyc` kernels take (ops.conv_needs_any) has no fused
+        Dropout, so the Dropout layer runs on its own.  Asked before an UpSampling1D fold is decided, so the folded pair (2 * filters at
+        stride 1) must not need them either -- for every 5-tap 'same' layer, folded or not: declining costs one pass, fusing wrongly an error.
+        (For <= 4 filters that also turns the NotImplementedError of the fused Dropout into an unfused Dropout on such pairs, e.g. 8 -> 3.)"""
+        k = getattr(self, 'kernel', None)
+        if k is None:
+            return True
+        Cin = self._run_cin(k.shape[1])
+        folded = self.can_fold_upsample() and self.stride == 1 and ops.conv_layer_needs_any(Cin, 2 * self.filters)
+        return not (ops.conv_layer_needs_any(Cin, self.filters) or folded)
 
     def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
         Layer.__init__(self, **kw)
@@ -126,6 +145,10 @@ class Conv1D(Layer):
                                       '(any stride >= 1 runs for <= 4 input channels)' % (self.stride, Cin))
         if not 1 <= self.k <= 40:
             raise NotImplementedError('Conv1D(kernel_size=%d): 1..40 taps (bbhMahoGANy.py:228 names 5 and 10)' % self.k)
+        if self.stride > 2 and ops.conv_needs_any(self._run_cin(Cin), self.filters):      # (its data gradient's phases have unit input stride)
+            raise NotImplementedError('Conv1D(%d filters, strides=%d) on %d input channels: strides above 2 run on the small-Cin kernels only, which '
+                                      'need a multiple of 4 filters; the any-channel kernels implement strides 1 and 2'
+                                      % (self.filters, self.stride, Cin))
         self.kernel = self.add_weight('kernel', glorot_uniform((self.k, Cin, self.filters)))
         self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
 
@@ -168,7 +191,10 @@ class Conv1D(Layer):
         fold = getattr(node, 'fold_up', None) is not None
         B = x.shape[0]
         bn_node = getattr(node, 'infer_bn', None)
-        if not ctx.training and bn_node is not None and x.shape[2] > 4:
+        # the pair of the conv that actually runs (after tap fold / upsample fold): when only the `anyc` kernels take it, every fusion that
+        # rests on a strict fused entry point is declined (folded BatchNormalization, epilogue statistics, Dropout, producer gradient)
+        anyc = ops.conv_layer_needs_any(self._run_cin(x.shape[2]), self.filters * (2 if fold and self.stride == 1 else 1))
+        if not ctx.training and bn_node is not None and x.shape[2] > 4 and not anyc:
             # inference phase: the following BatchNormalization (moving statistics) folds into the weights, its activation into the
             # epilogue: one kernel, and the pre-BN tensor is never written (generator.predict, bbhMahoGANy.py:1248)
             bn = bn_node.layer
@@ -192,7 +218,7 @@ class Conv1D(Layer):
         fused_drop = node.fused_drop is not None and self.filters > 4
         if node.fused_drop is not None and not fused_drop:
             raise NotImplementedError('Dropout directly after a Conv1D with <= 4 filters')
-        if ctx.training and bn_node is not None and x.shape[2] > 4 and Ce == self.filters and not _NO_CONVSTATS:
+        if ctx.training and bn_node is not None and x.shape[2] > 4 and Ce == self.filters and not _NO_CONVSTATS and not anyc:
             # training phase, linear conv whose only consumer is a BatchNormalization: its batch statistics come out of the conv kernel's
             # epilogue (no separate pass over the output); the BN node picks them up from ctx.bn_sums.  (Not for the two-phase folded
             # form, whose columns are (phase, channel): that BN layer runs its own statistics pass.)
@@ -200,7 +226,9 @@ class Conv1D(Layer):
             ctx.bn_sums[bn_node.index] = sums
             ctx.tape[node.index] = (x, y, a, pl, None, 0.0, w if fold else None, tf)
             return y
-        y, mask, rate = _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, a, (B, Lout, Ce))
+        if anyc and node.fused_drop is not None:      # not reachable through Sequential / Model: both build a layer before they plan it (fusable_drop)
+            raise NotImplementedError('Conv1D %s: a fused Dropout on a channel pair of the any-channel kernels (plan the model after building it)' % self.name)
+        y, mask, rate = _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, a, (B, Lout, Ce), anyc)
         ctx.tape[node.index] = (x, y, a, pl, mask, rate, w if fold else None, tf)   # x, y, mask in the shape of the conv that ran
         y = y.view(B, -1, self.filters)
         if ctx.training and (a[0] != 'linear' or mask is not None):
@@ -210,21 +238,22 @@ class Conv1D(Layer):
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
         x, y, a, pl, mask, rate, wf, tf = ctx.tape.pop(node.index)
         dy = _conv_bwd_epilogue(dy.contiguous().view(y.shape), y, a, mask, rate, ctx, node)
+        anyc = ops.conv_layer_needs_any(x.shape[2], y.shape[2])      # x, y: the conv that ran
         if tf is not None:
             # more than 5 taps: the gradients of the h-tap conv over (x, shifted x, ...) that ran, unfolded (csrc/tap_fold.hip)
             L0, pl0, w2 = tf
             if need_dw:
-                dw2, _ = ops.conv1d_wgrad(x, dy, w2.shape[0], self.stride, 0, None, self.bias.grad)
+                dw2, _ = ops.conv1d_wgrad(x, dy, w2.shape[0], self.stride, 0, None, self.bias.grad, any_channels=anyc)
                 ops.conv1d_tapunfold_dw(dw2, self.k, self.kernel.grad)
             if need_dx:
-                dx2 = ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w2), x.shape[1], self.stride, 0, None)
+                dx2 = ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w2), x.shape[1], self.stride, 0, None, any_channels=anyc)
                 return ops.conv1d_tapunfold_dx(dx2, L0, self.k, pl0)
             return None
         if need_dw:
             if wf is None:
-                ops.conv1d_wgrad(x, dy, self.k, self.stride, pl, self.kernel.grad, self.bias.grad)
+                ops.conv1d_wgrad(x, dy, self.k, self.stride, pl, self.kernel.grad, self.bias.grad, any_channels=anyc)
             else:
-                dwf, dbf = ops.conv1d_wgrad(x, dy, 3, 1, pl)
+                dwf, dbf = ops.conv1d_wgrad(x, dy, 3, 1, pl, any_channels=anyc)
                 ops.conv1d_up2_unfold_grad(dwf, dbf, self.filters, self.stride, self.kernel.grad, self.bias.grad)
         if need_dx:
             if prev is not None and ops.can_fuse_dgrad(x.shape[2], y.shape[2]):
@@ -236,8 +265,8 @@ class Conv1D(Layer):
                 # data gradient on the fly (ops.ConvGrad1); the (B, L, Cin) tensor is neither written here nor read there
                 return ops.ConvGrad1(dy, self.kernel.data, x.shape[1], pl)
             if wf is None:
-                return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(self.kernel.data), x.shape[1], self.stride, pl, prev)
-            return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(wf), x.shape[1], 1, pl, prev)
+                return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(self.kernel.data), x.shape[1], self.stride, pl, prev, any_channels=anyc)
+            return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(wf), x.shape[1], 1, pl, prev, any_channels=anyc)
         return None
 
 

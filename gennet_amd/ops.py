@@ -62,12 +62,25 @@ def conv_geometry(L, k, stride, padding):
 
 
 # ---------------------------------------------------------------------------------------------- conv / dense
-def conv1d_fwd(x, w, b, stride, pad_left, Lout, act='linear', act_param=0.0):
+def conv_needs_any(Cin, Cout):
+    """True when the strict forward and weight gradient refuse this channel pair (gn_conv1d_needs_any): only conv1d_fwd / conv1d_wgrad with
+    any_channels=True run it, on the `anyc` kernels (csrc/conv_anyc.hip), and no fused variant does.  A data gradient runs the swapped pair:
+    conv1d_dgrad of a (Cin, Cout) layer needs any_channels=True when conv_needs_any(Cout, Cin)."""
+    return _lib.predicate('gn_conv1d_needs_any', int(Cin), int(Cout))
+
+
+def conv_layer_needs_any(Cin, Cout):
+    """A (Cin, Cout) layer in any of its three directions: the pair, or the swapped pair its data gradient runs (3 -> 4: only the latter)."""
+    return conv_needs_any(Cin, Cout) or conv_needs_any(Cout, Cin)
+
+
+def conv1d_fwd(x, w, b, stride, pad_left, Lout, act='linear', act_param=0.0, any_channels=False):
+    """any_channels=True: gn_conv1d_fwd_any -- the same kernels with the same bits wherever the strict entry runs, plus the pairs it refuses."""
     _chk(x, w, b)
     B, L, Cin = x.shape
     k, _, Cout = w.shape
     y = torch.empty((B, Lout, Cout), dtype=torch.float32, device=x.device)
-    _lib.call('gn_conv1d_fwd', _p(x), _p(w), _p(b), _p(y), B, L, Cin, Cout, k, stride, pad_left, Lout, ACT[act], float(act_param), _stream())
+    _lib.call('gn_conv1d_fwd_any' if any_channels else 'gn_conv1d_fwd', _p(x), _p(w), _p(b), _p(y), B, L, Cin, Cout, k, stride, pad_left, Lout, ACT[act], float(act_param), _stream())
     return y
 
 
@@ -143,14 +156,17 @@ def conv1d_transpose_w(w):
     return wt
 
 
-def conv1d_dgrad(dy, wt, L, stride, pad_left, prev=None):
-    """prev = (y_prev, act, act_param, mask_prev, rate): fuse the producer layer's activation/dropout backward into the epilogue."""
+def conv1d_dgrad(dy, wt, L, stride, pad_left, prev=None, any_channels=False):
+    """prev = (y_prev, act, act_param, mask_prev, rate): fuse the producer layer's activation/dropout backward into the epilogue.
+    any_channels=True: gn_conv1d_dgrad_any (no fused form: prev must be None)."""
     _chk(dy, wt)
     B, Lout, Cout = dy.shape
     k, _, Cin = wt.shape
+    if any_channels and prev is not None:
+        raise ValueError('conv1d_dgrad(any_channels=True) has no fused producer gradient')
     dx = torch.empty((B, L, Cin), dtype=torch.float32, device=dy.device)
     if prev is None:
-        _lib.call('gn_conv1d_dgrad', _p(dy), _p(wt), _p(dx), B, L, Cin, Cout, k, stride, pad_left, Lout, _stream())
+        _lib.call('gn_conv1d_dgrad_any' if any_channels else 'gn_conv1d_dgrad', _p(dy), _p(wt), _p(dx), B, L, Cin, Cout, k, stride, pad_left, Lout, _stream())
     else:
         y_prev, act, param, mask, rate = prev
         _chk(y_prev, mask)
@@ -161,11 +177,12 @@ def conv1d_dgrad(dy, wt, L, stride, pad_left, prev=None):
 
 
 def can_fuse_dgrad(Cin, Cout):
-    return Cin > 4 and Cout > 4
+    return Cin > 4 and Cout > 4 and not conv_needs_any(Cin, Cout)
 
 
-def conv1d_wgrad(x, dy, k, stride, pad_left, dw=None, db=None, want_db=True):
-    """want_db=False: no bias gradient at all (db stays None; the kernels are handed NULL and skip the column sum of dy)."""
+def conv1d_wgrad(x, dy, k, stride, pad_left, dw=None, db=None, want_db=True, any_channels=False):
+    """want_db=False: no bias gradient at all (db stays None; the kernels are handed NULL and skip the column sum of dy).
+    any_channels=True: gn_conv1d_wgrad_any."""
     _chk(x, dy, dw, db)
     B, L, Cin = x.shape
     _, Lout, Cout = dy.shape
@@ -175,7 +192,7 @@ def conv1d_wgrad(x, dy, k, stride, pad_left, dw=None, db=None, want_db=True):
         db = torch.empty((Cout,), dtype=torch.float32, device=x.device)
     nb = _lib.size('gn_conv1d_wgrad_workspace', B, L, Cin, Cout, k, stride, Lout)
     ws = workspace(nb, x.device)
-    _lib.call('gn_conv1d_wgrad', _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(), B, L, Cin, Cout, k, stride, pad_left, Lout, _stream())
+    _lib.call('gn_conv1d_wgrad_any' if any_channels else 'gn_conv1d_wgrad', _p(x), _p(dy), _p(dw), _p(db), _p(ws), ws.numel(), B, L, Cin, Cout, k, stride, pad_left, Lout, _stream())
     return dw, db
 
 
@@ -778,7 +795,8 @@ def prof_reset():
 
 
 def prof_collect(kind=-1):
-    """kind 0: conv_mfma kernels (forward + data gradient), 1: wgrad_mfma_kernel, 2: bf16x3 conv (opt-in), 3: fused synthesiser, -1: all."""
+    """kind 0: conv_mfma kernels (forward + data gradient), 1: wgrad_mfma_kernel, 2: bf16x3 conv (opt-in), 3: fused synthesiser,
+    9: anyc forward-form launches (forward, data gradient, each phase of a strided one), 10: anyc weight gradient, -1: all."""
     import ctypes
     out = (ctypes.c_double * 4)()
     _lib.call('gn_prof_collect', int(kind), ctypes.cast(out, ctypes.c_void_p))

@@ -103,6 +103,23 @@ size_t gn_conv1d_wgrad_workspace(int B, int L, int Cin, int Cout, int k, int str
 int gn_conv1d_wgrad(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes,
                     int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream);
 
+/* ---- any channel pair ------------------------------------------------------------------------------------
+ * The entry points above are strict: Cin <= 4 needs Cout % 4 == 0 (the small-Cin kernels); otherwise Cout <= 4 needs Cin % 4 == 0 (the small-Cout
+ * kernels); otherwise both must be multiples of 4.  Any other pair is GN_EINVAL (callers that size their layers for the aligned kernels hear
+ * about it when a shape falls off them).  gn_conv1d_needs_any is that predicate for a forward or weight-gradient call of (Cin, Cout): 1 when
+ * the strict entry point refuses the pair.  gn_conv1d_dgrad runs the swapped pair: it refuses when gn_conv1d_needs_any(Cout, Cin).  The _any entry points take the same parameters, run every pair the strict ones take
+ * on the same kernels with the same bits, and the remaining pairs on the `anyc` kernels (csrc/conv_anyc.hip: exact fp32 on the matrix cores,
+ * k <= 5, strides 1 and 2, bias and activation epilogue; the weight gradient's partial sums are reduced in a fixed order).  The fused variants
+ * (dropout, producer gradient, statistics) have no _any form.  gn_conv1d_wgrad_workspace answers for every pair. */
+int gn_conv1d_needs_any(int Cin, int Cout);
+int gn_conv1d_fwd_any(const float* x, const float* w, const float* bias, float* y,
+                      int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout,
+                      int act, float act_param, void* stream);
+int gn_conv1d_dgrad_any(const float* dy, const float* wt, float* dx,
+                        int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream);
+int gn_conv1d_wgrad_any(const float* x, const float* dy, float* dw, float* db, void* ws, size_t ws_bytes,
+                        int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream);
+
 /* ---- width-2 Conv2D fold (bbhMahoGANy.py:439,:447: Conv2D(C,(5,5),strides=(2,1),padding='same') on (n,2,Cin)) ----
  * wf[kh, w*Cin+c, w2*Cout+c2] = w[kh, w-w2+2, c, c2];   biasf = [bias, bias]
  * unfold_grad: dw[kh,kw,c,c2] = sum over the (w,w2) blocks with w-w2+2 == kw (0 for kw in {0,4}); db = dbf[:Cout]+dbf[Cout:] */
@@ -336,7 +353,7 @@ int gn_bn_finalize_zero_debias_dyn(const double* sums, double count, const float
 int gn_prof_enable(int on);
 int gn_prof_reset(void);
 /* sums over launches since reset of one kernel family (kind 0 = conv_mfma_kernel: forward + data gradient,
- * 1 = wgrad_mfma_kernel, -1 = both): out[0] = launches, out[1] = total ms, out[2] = total algorithmic FLOP,
+ * 1 = wgrad_mfma_kernel, 9 = the anyc conv, 10 = the anyc weight gradient, -1 = all): out[0] = launches, out[1] = total ms, out[2] = total algorithmic FLOP,
  * out[3] = total algorithmic bytes (each operand read once, the result written once) */
 int gn_prof_collect(int kind, double* out4_host);
 
