@@ -480,6 +480,9 @@ class Node(object):
         self.index = -1
         self.out_shape = out_shape
         self.fuse_prev = -1                # producer node whose [activation -> dropout] backward this node's dgrad absorbs
+        self.fold_up = None                # the absorbed UpSampling1D node in front whose work is folded into this conv's weights
+        self.infer_bn = None               # the BatchNormalization consumer this conv absorbs in the inference phase
+        self.lazy_bn = -1                  # BatchNormalization producer that forms this 1-filter conv's data gradient in its own backward
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -885,7 +888,7 @@ class Model(Layer):
     # -- planning: consumers, peephole fusions
     def _plan(self):
         for n in self.nodes:
-            n.fused_act, n.fused_drop, n.absorbed = None, None, False
+            n.fused_act, n.fused_drop, n.absorbed, n.fuse_prev, n.fold_up, n.infer_bn, n.lazy_bn = None, None, False, -1, None, None, -1
         consumers = {n.index: [] for n in self.nodes}
         for n in self.nodes:
             for i in n.inbound:
@@ -914,9 +917,7 @@ class Model(Layer):
                     n.fused_drop = (c.layer.drop_rate, c.layer)
                     c.absorbed = True
         # UpSampling1D(2) whose only consumer is a 5-tap 'same' Conv1D: the pair runs as a 3-tap conv on the un-upsampled tensor with
-        # folded weights (layers.Conv1D._geometry); the upsample node passes its input through and nothing is materialised
-        for n in self.nodes:
-            n.fold_up = None
+        # folded weights (layers._ConvRun); the upsample node passes its input through and nothing is materialised
         for n in self.nodes:
             if n.absorbed or not getattr(n.layer, 'is_upsample2', False) or len(n.inbound) != 1 or n.inbound[0] < 0:
                 continue
@@ -927,7 +928,6 @@ class Model(Layer):
         # inference-phase fusion: a BatchNormalization that is the sole consumer of a linear conv folds into that conv's weights
         # (predict only: the training phase normalises with batch statistics)
         for n in self.nodes:
-            n.infer_bn = None
             if n.absorbed or not getattr(n.layer, 'can_fold_bn', False) or n.fused_act is not None or n.fused_drop is not None:
                 continue
             c = sole_consumer(n.index)
@@ -936,7 +936,6 @@ class Model(Layer):
         # backward fusion: node n's data gradient can carry the producer p's activation/dropout derivative in its epilogue when p's
         # output reaches n through shape-only nodes (absorbed activations, Flatten, Reshape) and nothing else consumes it
         for n in self.nodes:
-            n.fuse_prev = -1
             if n.absorbed or len(n.inbound) != 1 or not getattr(n.layer, 'can_absorb_prev_act_bwd', False):
                 continue
             cur, ok = n.inbound[0], True
@@ -950,7 +949,6 @@ class Model(Layer):
         # a 1-filter stride-1 Conv1D whose input comes from a BatchNormalization through absorbed nodes only (the generator's output
         # conv): its data gradient is not materialised, the BatchNormalization's backward passes form it on the fly (ops.ConvGrad1)
         for n in self.nodes:
-            n.lazy_bn = -1
             if n.absorbed or len(n.inbound) != 1 or n.fold_up is not None or not hasattr(n.layer, 'can_defer_dgrad'):
                 continue
             cur = n.inbound[0]

@@ -5,6 +5,8 @@ biases, BatchNormalization(axis=-1, epsilon=1e-3, gamma=1, beta=0, moving_mean=0
 Layers that the reference imports but never places on the hot path are not provided; asking for an unsupported
 configuration raises instead of silently running something else.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -25,16 +27,19 @@ def _check_init(kernel_initializer):
         raise NotImplementedError('kernel_initializer %r (only glorot_uniform is used on the hot path)' % (kernel_initializer,))
 
 
-def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any_channels=False):
-    """conv + activation epilogue, plus the following Dropout when the planner fused one (training phase only).  any_channels: the pair needs
-    the `anyc` kernels, which have no fused Dropout (the planner declined it: Conv1D.fusable_drop)."""
-    if any_channels:
-        return ops.conv1d_fwd(x, w, b, stride, pl, Lout, act[0], act[1], any_channels=True), None, 0.0
-    if node.fused_drop is not None and ctx.training and node.fused_drop[0] > 0.0:
-        rate, drop_layer = node.fused_drop
-        mask = drop_layer.make_mask(ctx, out_shape_for_mask)
-        return ops.conv1d_fwd_dropout(x, w, b, mask, stride, pl, Lout, act[0], act[1], rate), mask, rate
-    return ops.conv1d_fwd(x, w, b, stride, pl, Lout, act[0], act[1]), None, 0.0
+def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any_channels=False, drop_ok=True):
+    """conv + activation epilogue, and the one place that decides what becomes of a Dropout the planner fused onto the node: applied in the conv's
+    epilogue in the training phase; refused where the layer has none (drop_ok False: a Conv1D with <= 4 filters).  any_channels: the `anyc` kernels
+    have no fused Dropout, and none arrives: Conv1D.fusable_drop declined it (Sequential and Model build a layer before they plan it)."""
+    if node.fused_drop is not None:
+        assert not any_channels, 'a fused Dropout on a channel pair of the any-channel kernels (plan the model after building it)'
+        if not drop_ok:
+            raise NotImplementedError('Dropout directly after a Conv1D with <= 4 filters')
+        if ctx.training and node.fused_drop[0] > 0.0:
+            rate, drop_layer = node.fused_drop
+            mask = drop_layer.make_mask(ctx, out_shape_for_mask)
+            return ops.conv1d_fwd_dropout(x, w, b, mask, stride, pl, Lout, act[0], act[1], rate), mask, rate
+    return ops.conv1d_fwd(x, w, b, stride, pl, Lout, act[0], act[1], any_channels=any_channels), None, 0.0
 
 
 def _conv_bwd_epilogue(dy, y, act, mask, rate, ctx=None, node=None):
@@ -47,6 +52,71 @@ def _conv_bwd_epilogue(dy, y, act, mask, rate, ctx=None, node=None):
     if act[0] != 'linear':
         return ops.act_bwd(dy, y, act[0], act[1], inplace=True)
     return dy
+
+
+# A k-tap conv, 1 <= k <= 40, in its three directions.  More than 5 taps (`filtsize = 5 # 10 is best`, bbhMahoGANy.py:228) run as G = ceil(k/5) groups
+# of h = ceil(k/G) taps over the input with its shifted copies as further channel groups and the left padding materialised (csrc/tap_fold.hip): the
+# same <= 5-tap matrix-core kernels on 0 padding, the tap groups accumulating in their K loop; gradients come out folded and are unfolded.  Every
+# argument is that of the k-tap conv; folded=True: the caller kept that operand in its folded form, and it is not folded again.
+def _kconv_fwd(x, w, b, stride, pl, Lout, launch=ops.conv1d_fwd):
+    """-> (launch(x, w, b, stride, pl, Lout) on the operands as they are launched, those x and w)"""
+    if w.shape[0] > 5:
+        x, w, pl = ops.conv1d_tapfold_x(x, w.shape[0], pl), ops.conv1d_tapfold_w(w), 0
+    return launch(x, w, b, stride, pl, Lout), x, w
+
+
+def _kconv_dgrad(dy, w, k, L, stride, pl, prev=None, any_channels=False, folded=False):
+    """prev: the producer's [activation -> dropout] backward in the epilogue (ops.conv1d_dgrad), for <= 5 taps"""
+    if k <= 5:
+        return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w), L, stride, pl, prev, any_channels=any_channels)
+    assert prev is None
+    w2 = w if folded else ops.conv1d_tapfold_w(w)
+    return ops.conv1d_tapunfold_dx(ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w2), L + pl, stride, 0, None, any_channels=any_channels), L, k, pl)
+
+
+def _kconv_wgrad(x, dy, k, stride, pl, dw=None, db=None, want_db=True, any_channels=False, folded=False):
+    """-> (dw, db), written into the given tensors where given"""
+    if k <= 5:
+        return ops.conv1d_wgrad(x, dy, k, stride, pl, dw, db, want_db, any_channels)
+    x2 = x if folded else ops.conv1d_tapfold_x(x, k, pl)
+    dw2, db = ops.conv1d_wgrad(x2, dy, ops.tap_groups(k)[1], stride, 0, None, db, want_db, any_channels)
+    return ops.conv1d_tapunfold_dw(dw2, k, dw), db
+
+
+def _launched_pair(k, Cin, Cout, up_folded=False, stride=1):
+    """(Cin, Cout) of the conv that is launched for a k-tap Cin -> Cout layer: the tap fold puts its G tap groups side by side as input channels;
+    an UpSampling1D folded into a stride-1 layer makes the two output phases its columns."""
+    return Cin * ops.tap_groups(k)[0] if k > 5 else Cin, 2 * Cout if up_folded and stride == 1 else Cout
+
+
+class _ConvRun(object):
+    """The conv a Conv1D launches on (L, Cin) inputs, the UpSampling1D in front folded into it (Model._plan: node.fold_up) or not.  Whatever depends
+    on what is launched asks this record: the planner and build() one without L (channels only), the forward one that the backward finds on the tape.
+      k, stride, pl, Lout    the layer's own conv or, upsample folded, the 3-tap stride-1 conv on the un-upsampled input (ops.conv1d_up2_fold; for
+                             stride 1 its (L, 2 * filters) output is the layer's (2L, filters) output in memory)
+      tap_folded             k > 5: launched as tap_groups(k)[1] taps on 0 padding over L + pl rows (_kconv_*), gradients unfolded with (L, pl)
+      Cin_run, Cout_run      the launched channel pair; fwd_any: only the `anyc` kernels take it (ops.conv_needs_any); any_channels: it or the data
+                             gradient's swapped pair -- then no fusion that rests on a strict fused entry point is made"""
+    __slots__ = ('L', 'Cin', 'k', 'stride', 'pl', 'Lout', 'tap_folded', 'up_folded', 'Cin_run', 'Cout_run', 'fwd_any', 'any_channels')
+
+    def __init__(self, layer, Cin, up_folded, L=None):
+        self.L, self.Cin, self.up_folded, self.tap_folded = L, Cin, up_folded, layer.k > 5
+        self.k, self.stride = (3, 1) if up_folded else (layer.k, layer.stride)
+        self.Cin_run, self.Cout_run = _launched_pair(layer.k, Cin, layer.filters, up_folded, layer.stride)
+        self.fwd_any = ops.conv_needs_any(self.Cin_run, self.Cout_run)
+        self.any_channels = self.fwd_any or ops.conv_needs_any(self.Cout_run, self.Cin_run)
+        self.Lout, self.pl = (None, None) if L is None else (L, 1) if up_folded else ops.conv_geometry(L, layer.k, layer.stride, layer.padding)
+
+
+def _transpose_pair_ok(k, filters, Cin):
+    """Conv2DTranspose runs the adjoint Conv1D (filters -> Cin, tap-folded past 5 taps) on the strict entry points: both channel counts multiples of
+    4, or one side <= 4 and the other a multiple of 4.  (Wider than the library's own rule where both sides are <= 4: DESIGN 8c, known gap.)"""
+    a, b = _launched_pair(k, filters, Cin)
+    return (a % 4 == 0 and b % 4 == 0) or (a <= 4 and b % 4 == 0) or (b <= 4 and a % 4 == 0)
+
+
+# tape entry of the conv layers: x, y, mask in the shape of the conv that ran, w its kernel; run: Conv1D's record; pl, in_shape: Conv2D, Conv2DTranspose
+_ConvTape = collections.namedtuple('_ConvTape', 'x y act mask rate w run pl in_shape', defaults=(None, None, None, None))
 
 
 class Dense(Layer):
@@ -108,22 +178,16 @@ class Conv1D(Layer):
     offers_act_bwd = True
     can_absorb_prev_act_bwd = True
 
-    def _run_cin(self, Cin):
-        """input channels of the conv that actually runs: the tap fold puts its G tap groups side by side"""
-        return Cin * ops.tap_groups(self.k)[0] if self.k > 5 else Cin
-
     @property
     def fusable_drop(self):
-        """The planner (Model._plan) asks per instance: a channel pair that only the `anyc` kernels take (ops.conv_needs_any) has no fused
-        Dropout, so the Dropout layer runs on its own.  Asked before an UpSampling1D fold is decided, so the folded pair (2 * filters at
-        stride 1) must not need them either -- for every 5-tap 'same' layer, folded or not: declining costs one pass, fusing wrongly an error.
+        """The planner (Model._plan) asks per instance: a channel pair that only the `anyc` kernels take has no fused Dropout, so the Dropout layer
+        runs on its own.  Asked before an UpSampling1D fold is decided, so for every 5-tap 'same' layer neither the unfolded nor the folded pair
+        may need them, folded or not in the end: declining costs one pass, fusing wrongly an error.
         (For <= 4 filters that also turns the NotImplementedError of the fused Dropout into an unfused Dropout on such pairs, e.g. 8 -> 3.)"""
         k = getattr(self, 'kernel', None)
         if k is None:
             return True
-        Cin = self._run_cin(k.shape[1])
-        folded = self.can_fold_upsample() and self.stride == 1 and ops.conv_layer_needs_any(Cin, 2 * self.filters)
-        return not (ops.conv_layer_needs_any(Cin, self.filters) or folded)
+        return not any(_ConvRun(self, k.shape[1], up).any_channels for up in ((False, True) if self.can_fold_upsample() else (False,)))
 
     def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
         Layer.__init__(self, **kw)
@@ -145,7 +209,7 @@ class Conv1D(Layer):
                                       '(any stride >= 1 runs for <= 4 input channels)' % (self.stride, Cin))
         if not 1 <= self.k <= 40:
             raise NotImplementedError('Conv1D(kernel_size=%d): 1..40 taps (bbhMahoGANy.py:228 names 5 and 10)' % self.k)
-        if self.stride > 2 and ops.conv_needs_any(self._run_cin(Cin), self.filters):      # (its data gradient's phases have unit input stride)
+        if self.stride > 2 and _ConvRun(self, Cin, False).fwd_any:      # (its data gradient's phases have unit input stride)
             raise NotImplementedError('Conv1D(%d filters, strides=%d) on %d input channels: strides above 2 run on the small-Cin kernels only, which '
                                       'need a multiple of 4 filters; the any-channel kernels implement strides 1 and 2'
                                       % (self.filters, self.stride, Cin))
@@ -154,13 +218,6 @@ class Conv1D(Layer):
 
     def compute_output_shape(self, input_shape):
         return (ops.conv_geometry(input_shape[0], self.k, self.stride, self.padding)[0], self.filters)
-
-    def _tap_fold(self, x, w):
-        """More than 5 taps (`filtsize = 5 # 10 is best`, bbhMahoGANy.py:228) run as G = ceil(k/5) groups of h = ceil(k/G) taps over the input with its
-        shifted copies as further channel groups (csrc/tap_fold.hip): the same <= 5-tap matrix-core kernels, the tap groups accumulating in their K loop.
-        -> (x2, w2, (L, pad_left))"""
-        _, pl = ops.conv_geometry(x.shape[1], self.k, self.stride, self.padding)
-        return ops.conv1d_tapfold_x(x, self.k, pl), ops.conv1d_tapfold_w(w), (x.shape[1], pl)
 
     @property
     def can_fold_bn(self):
@@ -174,100 +231,64 @@ class Conv1D(Layer):
         """UpSampling1D(2) in front folds into the weights (ops.conv1d_up2_fold): the engine's planner asks."""
         return self.k == 5 and self.padding == 'same' and self.stride in (1, 2) and not _NO_UPFOLD
 
-    def _geometry(self, node, x, w, b):
-        """(w, b, k, stride, pad_left, Lout, Cout) of the conv that actually runs on x: the layer's own, or -- with the upsample in front
-        folded (node.fold_up) -- the 3-tap stride-1 conv on the un-upsampled input; for stride 1 its (L, 2*filters) output is the layer's
-        (2L, filters) output in memory."""
-        if getattr(node, 'fold_up', None) is None:
-            Lout, pl = ops.conv_geometry(x.shape[1], self.k, self.stride, self.padding)
-            if self.k > 5:                  # w is the tap-folded kernel, x will be (forward: _tap_fold)
-                return w, b, ops.tap_groups(self.k)[1], self.stride, 0, Lout, self.filters
-            return w, b, self.k, self.stride, pl, Lout, self.filters
-        wf, bf = ops.conv1d_up2_fold(w, b, self.stride)
-        return wf, bf, 3, 1, 1, x.shape[1], wf.shape[2]
+    def _launch(self, run, x, w, b, launch):
+        """`launch` (_kconv_fwd) on the operands of the conv that runs: tap-folded (k > 5), or the kernel with the upsample folded in (k == 5)"""
+        if run.up_folded:
+            w, b = ops.conv1d_up2_fold(w, b, self.stride)
+        return _kconv_fwd(x, w, b, run.stride, run.pl, run.Lout, launch)
 
     def forward(self, ctx, node, x):
         a = node.fused_act or self.activation
-        fold = getattr(node, 'fold_up', None) is not None
         B = x.shape[0]
-        bn_node = getattr(node, 'infer_bn', None)
-        # the pair of the conv that actually runs (after tap fold / upsample fold): when only the `anyc` kernels take it, every fusion that
-        # rests on a strict fused entry point is declined (folded BatchNormalization, epilogue statistics, Dropout, producer gradient)
-        anyc = ops.conv_layer_needs_any(self._run_cin(x.shape[2]), self.filters * (2 if fold and self.stride == 1 else 1))
-        if not ctx.training and bn_node is not None and x.shape[2] > 4 and not anyc:
-            # inference phase: the following BatchNormalization (moving statistics) folds into the weights, its activation into the
-            # epilogue: one kernel, and the pre-BN tensor is never written (generator.predict, bbhMahoGANy.py:1248)
+        run = _ConvRun(self, x.shape[2], node.fold_up is not None, x.shape[1])
+        bn_node = None if run.any_channels else node.infer_bn
+        if not ctx.training and bn_node is not None and run.Cin > 4:
+            # inference phase: the following BatchNormalization (moving statistics) folds into the layer's own kernel, its activation into the
+            # epilogue: one kernel, and the pre-BN tensor is never written (generator.predict, bbhMahoGANy.py:1248).  (Asks for the layer's own
+            # Cin > 4, the statistics below for the launched one: they differ for a tap-folded layer on <= 4 channels, as they always have.)
             bn = bn_node.layer
             scale, shift = ops.bn_infer_coeffs(bn.gamma.data, bn.beta.data, bn.moving_mean.data, bn.moving_variance.data, bn.epsilon)
-            w2, b2 = ops.conv_fold_bn(self.kernel.data, self.bias.data, scale, shift)
-            xin = x
-            if self.k > 5:
-                x, w2, _ = self._tap_fold(x, w2)
-            w2, b2, _, stride, pl, Lout, _ = self._geometry(node, xin, w2, b2)
+            w, b = ops.conv_fold_bn(self.kernel.data, self.bias.data, scale, shift)
             act = bn_node.fused_act or ('linear', 0.0)
             ctx.skip.add(bn_node.index)
-            return ops.conv1d_fwd(x, w2, b2, stride, pl, Lout, act[0], act[1]).view(B, -1, self.filters)
-        tf = None
-        if self.k > 5:
-            xin = x
-            x, w2, tf = self._tap_fold(x, self.kernel.data)
-            w, b, k, stride, pl, Lout, Ce = self._geometry(node, xin, w2, self.bias.data)
-            tf = tf + (w2,)
-        else:
-            w, b, k, stride, pl, Lout, Ce = self._geometry(node, x, self.kernel.data, self.bias.data)
-        fused_drop = node.fused_drop is not None and self.filters > 4
-        if node.fused_drop is not None and not fused_drop:
-            raise NotImplementedError('Dropout directly after a Conv1D with <= 4 filters')
-        if ctx.training and bn_node is not None and x.shape[2] > 4 and Ce == self.filters and not _NO_CONVSTATS and not anyc:
+            return self._launch(run, x, w, b, lambda *conv: ops.conv1d_fwd(*conv, act[0], act[1]))[0].view(B, -1, self.filters)
+        if ctx.training and bn_node is not None and run.Cin_run > 4 and run.Cout_run == self.filters and not _NO_CONVSTATS:
             # training phase, linear conv whose only consumer is a BatchNormalization: its batch statistics come out of the conv kernel's
             # epilogue (no separate pass over the output); the BN node picks them up from ctx.bn_sums.  (Not for the two-phase folded
             # form, whose columns are (phase, channel): that BN layer runs its own statistics pass.)
-            y, sums = ops.conv1d_fwd_stats(x, w, b, stride, pl, Lout)
+            (y, sums), x, w = self._launch(run, x, self.kernel.data, self.bias.data, ops.conv1d_fwd_stats)
             ctx.bn_sums[bn_node.index] = sums
-            ctx.tape[node.index] = (x, y, a, pl, None, 0.0, w if fold else None, tf)
+            ctx.tape[node.index] = _ConvTape(x, y, a, None, 0.0, w, run)
             return y
-        if anyc and node.fused_drop is not None:      # not reachable through Sequential / Model: both build a layer before they plan it (fusable_drop)
-            raise NotImplementedError('Conv1D %s: a fused Dropout on a channel pair of the any-channel kernels (plan the model after building it)' % self.name)
-        y, mask, rate = _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, a, (B, Lout, Ce), anyc)
-        ctx.tape[node.index] = (x, y, a, pl, mask, rate, w if fold else None, tf)   # x, y, mask in the shape of the conv that ran
+        (y, mask, rate), x, w = self._launch(run, x, self.kernel.data, self.bias.data, lambda *conv: _conv_fwd(
+            node, ctx, *conv, a, (B, run.Lout, run.Cout_run), run.any_channels, self.filters > 4))
+        ctx.tape[node.index] = _ConvTape(x, y, a, mask, rate, w, run)
         y = y.view(B, -1, self.filters)
         if ctx.training and (a[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
-        x, y, a, pl, mask, rate, wf, tf = ctx.tape.pop(node.index)
-        dy = _conv_bwd_epilogue(dy.contiguous().view(y.shape), y, a, mask, rate, ctx, node)
-        anyc = ops.conv_layer_needs_any(x.shape[2], y.shape[2])      # x, y: the conv that ran
-        if tf is not None:
-            # more than 5 taps: the gradients of the h-tap conv over (x, shifted x, ...) that ran, unfolded (csrc/tap_fold.hip)
-            L0, pl0, w2 = tf
-            if need_dw:
-                dw2, _ = ops.conv1d_wgrad(x, dy, w2.shape[0], self.stride, 0, None, self.bias.grad, any_channels=anyc)
-                ops.conv1d_tapunfold_dw(dw2, self.k, self.kernel.grad)
-            if need_dx:
-                dx2 = ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(w2), x.shape[1], self.stride, 0, None, any_channels=anyc)
-                return ops.conv1d_tapunfold_dx(dx2, L0, self.k, pl0)
-            return None
-        if need_dw:
-            if wf is None:
-                ops.conv1d_wgrad(x, dy, self.k, self.stride, pl, self.kernel.grad, self.bias.grad, any_channels=anyc)
-            else:
-                dwf, dbf = ops.conv1d_wgrad(x, dy, 3, 1, pl, any_channels=anyc)
+        t = ctx.tape.pop(node.index)
+        run = t.run
+        dy = _conv_bwd_epilogue(dy.contiguous().view(t.y.shape), t.y, t.act, t.mask, t.rate, ctx, node)
+        if need_dw:         # t.x, t.w: as the forward launched them, folds included
+            if run.up_folded:
+                dwf, dbf = _kconv_wgrad(t.x, dy, run.k, run.stride, run.pl, any_channels=run.any_channels)
                 ops.conv1d_up2_unfold_grad(dwf, dbf, self.filters, self.stride, self.kernel.grad, self.bias.grad)
-        if need_dx:
-            if prev is not None and ops.can_fuse_dgrad(x.shape[2], y.shape[2]):
-                ctx.pre_applied.add(node.fuse_prev)
             else:
-                prev = None
-            if getattr(node, 'lazy_bn', -1) >= 0:
-                # 1 filter, stride 1, and the input comes straight from a BatchNormalization: that layer's backward passes form this
-                # data gradient on the fly (ops.ConvGrad1); the (B, L, Cin) tensor is neither written here nor read there
-                return ops.ConvGrad1(dy, self.kernel.data, x.shape[1], pl)
-            if wf is None:
-                return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(self.kernel.data), x.shape[1], self.stride, pl, prev, any_channels=anyc)
-            return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(wf), x.shape[1], 1, pl, prev, any_channels=anyc)
-        return None
+                _kconv_wgrad(t.x, dy, run.k, run.stride, run.pl, self.kernel.grad, self.bias.grad, any_channels=run.any_channels, folded=True)
+        if not need_dx:
+            return None
+        if prev is not None and not run.tap_folded and ops.can_fuse_dgrad(run.Cin_run, run.Cout_run):
+            ctx.pre_applied.add(node.fuse_prev)
+        else:
+            prev = None
+        if node.lazy_bn >= 0:
+            # 1 filter, stride 1, and the input comes straight from a BatchNormalization: that layer's backward passes form this
+            # data gradient on the fly (ops.ConvGrad1); the (B, L, Cin) tensor is neither written here nor read there
+            return ops.ConvGrad1(dy, self.kernel.data, run.L, run.pl)
+        return _kconv_dgrad(dy, t.w, run.k, run.L, run.stride, run.pl, prev, run.any_channels, folded=True)
 
 
 class Conv2D(Layer):
@@ -307,24 +328,24 @@ class Conv2D(Layer):
         wf, bf = ops.conv2d_w2_fold(self.kernel.data, self.bias.data)
         xf = x.reshape(B, H, 2 * Cin)
         y, mask, rate = _conv_fwd(node, ctx, xf, wf, bf, self.sh, pl, Lout, a, (B, Lout, 2, self.filters))
-        ctx.tape[node.index] = (xf, y, a, pl, wf, Cin, mask, rate)
+        ctx.tape[node.index] = _ConvTape(xf, y, a, mask, rate, wf, pl=pl, in_shape=x.shape)
         if ctx.training and (a[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], mask, rate)
         return y.reshape(B, Lout, 2, self.filters)
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
-        xf, y, a, pl, wf, Cin, mask, rate = ctx.tape.pop(node.index)
-        dy = _conv_bwd_epilogue(dy.contiguous().reshape(y.shape), y, a, mask, rate, ctx, node)
+        t = ctx.tape.pop(node.index)
+        Cin = t.in_shape[3]
+        dy = _conv_bwd_epilogue(dy.contiguous().reshape(t.y.shape), t.y, t.act, t.mask, t.rate, ctx, node)
         if need_dw:
-            dwf, dbf = ops.conv1d_wgrad(xf, dy, self.kh, self.sh, pl)
+            dwf, dbf = ops.conv1d_wgrad(t.x, dy, self.kh, self.sh, t.pl)
             ops.conv2d_w2_unfold_grad(dwf, dbf, Cin, self.filters, self.kernel.grad, self.bias.grad)
         if need_dx:
             if prev is not None and ops.can_fuse_dgrad(2 * Cin, 2 * self.filters):
                 ctx.pre_applied.add(node.fuse_prev)
             else:
                 prev = None
-            dx = ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(wf), xf.shape[1], self.sh, pl, prev)
-            return dx.reshape(xf.shape[0], xf.shape[1], 2, Cin)
+            return ops.conv1d_dgrad(dy, ops.conv1d_transpose_w(t.w), t.x.shape[1], self.sh, t.pl, prev).reshape(t.in_shape)
         return None
 
 
@@ -372,10 +393,7 @@ class Conv2DTranspose(Layer):
     def build(self, input_shape):
         if len(input_shape) != 3:
             raise ValueError('Conv2DTranspose expects (batch, H, W, channels) inputs, got %r' % (tuple(input_shape),))
-        # the adjoint conv's channels (its input: filters, tap-folded to G * filters past 5 taps; its output: Cin) must suit a conv kernel family:
-        # both multiples of 4, or one side <= 4 and the other a multiple of 4
-        a, b = ops.tap_groups(self.k)[0] * self.filters if self.k > 5 else self.filters, input_shape[2]
-        if not ((a % 4 == 0 and b % 4 == 0) or (a <= 4 and b % 4 == 0) or (b <= 4 and a % 4 == 0)):
+        if not _transpose_pair_ok(self.k, self.filters, input_shape[2]):
             raise NotImplementedError('Conv2DTranspose(%d filters, kernel (1, %d)) on %d input channels: the conv kernels need both channel counts '
                                       'multiples of 4, or one of them <= 4 and the other a multiple of 4' % (self.filters, self.k, input_shape[2]))
         # keras' layout (1, kw, filters, Cin): glorot limit sqrt(6 / ((filters + Cin) kw)), and .h5 reads / writes are plain copies
@@ -389,9 +407,6 @@ class Conv2DTranspose(Layer):
     def compute_output_shape(self, input_shape):
         return (input_shape[0], self.out_length(input_shape[1]), self.filters)
 
-    def _pad_left(self, Wout):
-        return ops.conv_geometry(Wout, self.k, self.stride, self.padding)[1]
-
     def _act(self, node):
         if node.fused_act is not None and self.activation[0] != 'linear':
             raise NotImplementedError('Conv2DTranspose(activation=...) followed by another activation layer')
@@ -401,14 +416,10 @@ class Conv2DTranspose(Layer):
         a = self._act(node)
         B, H, W, Cin = x.shape
         Wout = self.out_length(W)
-        pl = self._pad_left(Wout)
+        pl = ops.conv_geometry(Wout, self.k, self.stride, self.padding)[1]
         x3 = x.contiguous().view(B * H, W, Cin)
         wadj = self.kernel.data.view(self.k, self.filters, Cin)         # the adjoint Conv1D's kernel (k, Cin=filters, Cout=Cin), no copy
-        if self.k > 5:
-            w2 = ops.conv1d_tapfold_w(wadj)
-            y = ops.conv1d_tapunfold_dx(ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(w2), Wout + pl, self.stride, 0), Wout, self.k, pl)
-        else:
-            y = ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(wadj), Wout, self.stride, pl)
+        y = _kconv_dgrad(x3, wadj, self.k, Wout, self.stride, pl)
         mask, rate = None, 0.0
         if ctx.training and node.fused_drop is not None and node.fused_drop[0] > 0.0:
             rate, drop_layer = node.fused_drop
@@ -420,31 +431,21 @@ class Conv2DTranspose(Layer):
                 ops.bias_act_dropout(y, self.bias.data, a[0], a[1], mask, rate)
         else:
             ops.bias_act_dropout(y, self.bias.data, a[0], a[1])
-        ctx.tape[node.index] = (x3, y, a, pl, mask, rate, (B, H, W, Cin))
+        ctx.tape[node.index] = _ConvTape(x3, y, a, mask, rate, wadj, pl=pl, in_shape=x.shape)
         y = y.view(B, H, Wout, self.filters)
         if ctx.training and (a[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
-        x3, y, a, pl, mask, rate, xshape = ctx.tape.pop(node.index)
-        dy = _conv_bwd_epilogue(dy.contiguous().view(y.shape), y, a, mask, rate, ctx, node)      # (B*H, Wout, filters)
-        W = x3.shape[1]
-        wadj = self.kernel.data.view(self.k, self.filters, x3.shape[2])
-        if need_dw:
+        t = ctx.tape.pop(node.index)
+        dy = _conv_bwd_epilogue(dy.contiguous().view(t.y.shape), t.y, t.act, t.mask, t.rate, ctx, node)      # (B*H, Wout, filters)
+        if need_dw:         # the adjoint's bias: none
             ops.bias_grad(dy.view(-1, self.filters), self.bias.grad)
-            if self.k > 5:
-                dw2, _ = ops.conv1d_wgrad(ops.conv1d_tapfold_x(dy, self.k, pl), x3, ops.tap_groups(self.k)[1], self.stride, 0, want_db=False)
-                ops.conv1d_tapunfold_dw(dw2, self.k, self.kernel.grad.view(wadj.shape))
-            else:
-                ops.conv1d_wgrad(dy, x3, self.k, self.stride, pl, self.kernel.grad.view(wadj.shape), want_db=False)   # the adjoint's bias: none
+            _kconv_wgrad(dy, t.x, self.k, self.stride, t.pl, self.kernel.grad.view(t.w.shape), want_db=False)
         if not need_dx:
             return None
-        if self.k > 5:
-            dx = ops.conv1d_fwd(ops.conv1d_tapfold_x(dy, self.k, pl), ops.conv1d_tapfold_w(wadj), None, self.stride, 0, W)
-        else:
-            dx = ops.conv1d_fwd(dy, wadj, None, self.stride, pl, W)
-        return dx.view(xshape)
+        return _kconv_fwd(dy, t.w, None, self.stride, t.pl, t.x.shape[1])[0].view(t.in_shape)
 
 
 BN_MOVING_AVERAGE = 'tf_zero_debias'       # default form of the moving-statistics update (BatchNormalization docstring)

@@ -130,16 +130,10 @@ def test_each_direction_reaches_the_family_of_the_adjoint_conv1d(B, H, W, Cin, F
         _, fwd = CF.launches(lambda: layer.forward(ctx, node, x))
         saved = ctx.tape[0]
         x3, dy3 = x.view(B * H, W, Cin), dy.view(B * H, Wout, Fl)
-        if kw > 5:          # the adjoint Conv1D as Conv1D runs it past 5 taps: h-tap groups over the folded input
-            h = ops.tap_groups(kw)[1]
-            w2 = ops.conv1d_tapfold_w(wadj)
-            adj_dgrad = lambda: ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(w2), Wout + pl, s, 0)              # noqa: E731
-            adj_fwd = lambda: ops.conv1d_fwd(ops.conv1d_tapfold_x(dy3, kw, pl), w2, None, s, 0, W)              # noqa: E731
-            adj_wgrad = lambda: ops.conv1d_wgrad(ops.conv1d_tapfold_x(dy3, kw, pl), x3, h, s, 0, want_db=False)  # noqa: E731
-        else:
-            adj_dgrad = lambda: ops.conv1d_dgrad(x3, ops.conv1d_transpose_w(wadj), Wout, s, pl)                 # noqa: E731
-            adj_fwd = lambda: ops.conv1d_fwd(dy3, wadj, None, s, pl, W)                                          # noqa: E731
-            adj_wgrad = lambda: ops.conv1d_wgrad(dy3, x3, kw, s, pl, want_db=False)                              # noqa: E731
+        # the adjoint Conv1D (kw taps, Fl -> Cin, stride s, pad pl over Wout rows) as Conv1D runs it: past 5 taps, h-tap groups over the folded input
+        adj_dgrad = lambda: L._kconv_dgrad(x3, wadj, kw, Wout, s, pl)                   # noqa: E731
+        adj_fwd = lambda: L._kconv_fwd(dy3, wadj, None, s, pl, W)                       # noqa: E731
+        adj_wgrad = lambda: L._kconv_wgrad(dy3, x3, kw, s, pl, want_db=False)           # noqa: E731
         assert fwd == CF.launches(adj_dgrad)[1]
         # data gradient alone, then weight gradient alone
         _, bwd_dx = CF.launches(lambda: layer.backward(ctx, node, dy, True, False))
