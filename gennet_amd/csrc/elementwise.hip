@@ -244,7 +244,10 @@ int axpy(float* y, const float* x, float a, size_t n, hipStream_t s) {
   return check_launch("axpy");
 }
 
-__global__ void fill_uniform_kernel(float* __restrict__ out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ base) {
+// [lo, hi): u <= 1 - 2^-24, but lo + (hi - lo) * u can still round up to hi (e.g. (20, 35), (0.5, 1)), so the value is held at top = the largest
+// float below hi (computed by the host); a value already below hi keeps its bits
+__global__ void fill_uniform_kernel(float* __restrict__ out, size_t n, float lo, float hi, float top, uint64_t seed, uint64_t offset,
+                                    const uint64_t* __restrict__ base) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t n4 = (n + 3) >> 2;
   if (base) offset += *base;
@@ -253,7 +256,7 @@ __global__ void fill_uniform_kernel(float* __restrict__ out, size_t n, float lo,
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const size_t k = 4 * i + e;
-      if (k < n) out[k] = lo + (hi - lo) * u01_24(r.v[e]);
+      if (k < n) out[k] = fminf(lo + (hi - lo) * u01_24(r.v[e]), top);
     }
   }
 }
@@ -286,7 +289,8 @@ __global__ void fill_normal_kernel(float* __restrict__ out, size_t n, float mean
 }
 int fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, hipStream_t s) {
   if (!n) return GN_OK;
-  hipLaunchKernelGGL(fill_uniform_kernel, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, s, out, n, lo, hi, seed, offset, rng_base());
+  hipLaunchKernelGGL(fill_uniform_kernel, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, s, out, n, lo, hi, lo < hi ? nextafterf(hi, lo) : INFINITY, seed, offset,
+                     rng_base());
   return check_launch("fill_uniform");
 }
 int fill_normal(float* out, size_t n, float mean, float sd, uint64_t seed, uint64_t offset, hipStream_t s, const float* sd_dev) {

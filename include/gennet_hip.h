@@ -219,7 +219,9 @@ int gn_affine_stack_bwd(const float* dimg, float a0, float a1, float* dx, int B,
 /* discriminator batch assembly (bbhMahoGANy.py:1268-1289): sX (2B, n, 2, 1): rows [0,B) = [real[b,t], noise[b,t]], rows [B,2B) =
  * [fake[j,t], event[t]-fake[j,t]] with j = 2B-1-row (the reference's np.append prepends, so the fake half is in reversed order) */
 int gn_assemble_d_batch(const float* real, const float* noise, const float* fake, const float* event, float* sX, int B, int n, void* stream);
-/* uniform(lo,hi) and normal(mean,std) fills from Philox (host RNG replacement for bbhMahoGANy.py:1161,1247,1277,1295) */
+/* uniform [lo, hi) and normal(mean,std) fills from Philox (host RNG replacement for bbhMahoGANy.py:1161,1247,1277,1295).  gn_fill_uniform, lo < hi:
+ * element i = min(lo + (hi - lo) u, the largest float below hi), u = (word >> 8) / 2^24 of counter (offset + i/4), lane i%4 -- half-open for every
+ * range, like numpy's uniform and Keras' random_uniform (the sum alone rounds up to hi at u = 1 - 2^-24 for ranges such as (20, 35)). */
 int gn_fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, void* stream);
 int gn_fill_normal(float* out, size_t n, float mean, float std, uint64_t seed, uint64_t offset, void* stream);
 /* Keras 2.2.4 noise layers (layers/noise.py), one pass each with the draw made in the same pass: element i uses Philox4x32-10 counter
