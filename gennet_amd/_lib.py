@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libgennet_hip.so')
 
 _lib = None
 
-vp, i32, f32, f64, u64, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_uint64, C.c_size_t
+vp, i32, i64, f32, f64, u64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_uint64, C.c_size_t
 
 _SIGS = {
     'gn_conv1d_fwd': [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
@@ -74,6 +74,7 @@ _SIGS = {
     'gn_bn_bwd_apply_conv1': [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, vp, sz, i32, i32, f32, f32, vp, vp, vp],
     'gn_bce_loss': [vp, vp, vp, vp, i32, i32, vp],
     'gn_mse_loss': [vp, vp, vp, vp, i32, i32, vp],
+    'gn_loss_pass': [i32, vp, vp, vp, vp, i64, i32, f64, vp, sz, vp],
     'gn_adam_step': [vp, vp, vp, vp, sz, f32, f32, f32, f32, vp],
     'gn_set_rng_base': [vp],
     'gn_adam_step_dyn': [vp, vp, vp, vp, sz, vp, f32, f32, f32, vp],
@@ -114,6 +115,7 @@ _SIZE_FNS = {
     'gn_bias_grad_workspace': [sz, i32],
     'gn_conv1d_fwd_stats_workspace': [i32, i32, i32],
     'gn_optim_sumsq_slots': [sz],
+    'gn_loss_pass_workspace': [i64, i32],
 }
 
 

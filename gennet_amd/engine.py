@@ -7,6 +7,8 @@ Mirrors the Keras 2.2.4 surface that BBH_version/bbhMahoGANy.py uses (SURVEY sec
   * model.trainable / layer.trainable assignment with COLLECT-AT-COMPILE semantics (:797-809, :1104-1115)
   * compile(loss=, optimizer=Adam(lr=, beta_1=), metrics=['accuracy']) (:1101-1119); one optimizer state per compiled model
   * train_on_batch(x, y) -> [loss, *metrics] python floats, keras ordering for multi-output models (:1165, :1292, :1296)
+  * every Keras loss name / alias / keras.losses callable, loss_weights=[...], several metrics; test_on_batch, evaluate, predict_on_batch
+    (ops.loss_pass)
   * predict(x) -> ndarray | [ndarray] (default batch_size 32) (:1185, :1248, :1343); learning phase 1 in train_on_batch for
     the WHOLE graph, 0 in predict
   * save / save_weights / load_weights / load_model (:1135-1142, :1173, :1373-1375)
@@ -766,7 +768,33 @@ def _get_optimizer(opt):
     return opt
 
 
-LOSSES = ('binary_crossentropy', 'mean_squared_error')
+LOSSES = tuple(k for k in ops.LOSS_KINDS if k != 'categorical_accuracy')
+OLD_KERNEL_LOSSES = ('binary_crossentropy', 'mean_squared_error')      # the one-block kernel of ops.loss, kept below ops.LOSS_PASS_MIN_ELEMENTS
+ACC_METRICS = ('accuracy', 'acc', 'binary_accuracy')                   # the hit count round(p) == y that every loss call returns
+PASS_METRICS = ('categorical_accuracy', 'mean_absolute_error', 'mean_squared_error', 'mean_absolute_percentage_error',
+                'mean_squared_logarithmic_error', 'cosine_proximity')
+
+
+def _named_fn(name):
+    def fn(y_true, y_pred):
+        raise NotImplementedError('%s names a HIP loss pass for compile(loss= / metrics=); there is no tensor runtime to call it on' % name)
+    fn.__name__ = fn.__qualname__ = name
+    fn.__doc__ = 'keras.losses.%s: pass it (or its name) to compile()' % name
+    return fn
+
+
+# keras.losses / keras.metrics of the facade: one callable per kind, its aliases the same object (as in Keras); compile() knows them by identity
+LOSS_FUNCTIONS = dict((k, _named_fn(k)) for k in ops.LOSS_KINDS)
+LOSS_FUNCTIONS.update((a, LOSS_FUNCTIONS[k]) for a, k in ops.LOSS_ALIASES.items())
+_FN_NAMES = dict((id(fn), k) for k, fn in LOSS_FUNCTIONS.items() if k in ops.LOSS_KINDS)
+
+
+def _loss_name(l):
+    """The kind of ops.LOSS_KINDS that a name, an alias or a facade callable stands for; None for anything else."""
+    if callable(l):
+        return _FN_NAMES.get(id(l))
+    k = ops.LOSS_ALIASES.get(l, l) if isinstance(l, str) else None
+    return k if k in ops.LOSS_KINDS else None
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -784,6 +812,8 @@ class Model(Layer):
         self.optimizer = None
         self.loss = None
         self.metrics = []
+        self.loss_weights = None
+        self._acc, self._metric_kinds = False, []
         self._train_params = None
         self.data_parallel = None
         if inputs is not None:
@@ -1008,25 +1038,44 @@ class Model(Layer):
     # Model used as a layer inside another graph is expanded by _append, so forward/backward are never called on it.
 
     # -- keras training surface
-    def compile(self, loss=None, optimizer=None, metrics=None, data_parallel=None, **kwargs):
-        """Collects the trainable weights NOW (keras semantics): later changes of .trainable do not affect this model."""
+    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, data_parallel=None, **kwargs):
+        """Collects the trainable weights NOW (keras semantics): later changes of .trainable do not affect this model.
+        loss: per output a name or alias of LOSSES, a keras.losses callable of the facade, or a callable squared error (K.lower_loss);
+        loss_weights: a list, one weight per output; metrics: any of ACC_METRICS / PASS_METRICS (names, aliases, facade callables)."""
         self.loss = loss
         n_out = len(self.output_ids)
         losses = list(loss) if isinstance(loss, (list, tuple)) else [loss] * n_out
         self._loss_scales = []
         for k, l in enumerate(losses):
             scale = 1.0
-            if callable(l):                # e.g. the script's chisquare_Loss (bbhMahoGANy.py:146-162): traced once and lowered
+            name = _loss_name(l)
+            if name is not None and name != 'categorical_accuracy':
+                losses[k] = name
+            elif callable(l):              # e.g. the script's chisquare_Loss (bbhMahoGANy.py:146-162): traced once and lowered
                 from .keras import backend as K
                 losses[k], scale = K.lower_loss(l)
-            elif l not in LOSSES:
-                raise NotImplementedError('loss %r: only %s (or a callable squared-error loss) run on the HIP path' % (l, LOSSES))
+            else:
+                raise NotImplementedError('loss %r: only %s, their aliases %s (or a callable squared-error loss) run on the HIP path'
+                                          % (l, LOSSES, tuple(sorted(ops.LOSS_ALIASES))))
             self._loss_scales.append(scale)
         self._losses = losses
+        if isinstance(loss_weights, dict):
+            raise NotImplementedError('loss_weights as a dict: pass a list, one weight per output')
+        if loss_weights is not None and len(loss_weights) != n_out:
+            raise ValueError('loss_weights has %d entries for %d outputs' % (len(loss_weights), n_out))
+        self.loss_weights = None if loss_weights is None else [float(w) for w in loss_weights]
+        self._loss_w = self.loss_weights or [1.0] * n_out
         self.metrics = list(metrics or [])
+        self._acc, self._metric_kinds = False, []     # the hit-count accuracy (one column, however often it is named) / the loss-pass metrics
         for m in self.metrics:
-            if m not in ('accuracy', 'acc', 'binary_accuracy'):
-                raise NotImplementedError('metric %r' % (m,))
+            name = _loss_name(m)
+            if not callable(m) and m in ACC_METRICS:
+                self._acc = True
+            elif name in PASS_METRICS:
+                if name not in self._metric_kinds:
+                    self._metric_kinds.append(name)
+            else:
+                raise NotImplementedError('metric %r: only %s and %s (or their aliases)' % (m, ACC_METRICS, PASS_METRICS))
         self.optimizer = _get_optimizer(optimizer)
         params, seen = [], set()
         if self.trainable:
@@ -1070,8 +1119,8 @@ class Model(Layer):
         if n_out > 1:
             names += ['out%d_loss' % k for k in range(n_out)]
         for k in range(n_out):
-            if self.metrics:
-                names.append('acc' if n_out == 1 else 'out%d_acc' % k)
+            for m in (['acc'] if self._acc else []) + self._metric_kinds:
+                names.append(m if n_out == 1 else 'out%d_%s' % (k, m))
         return names
 
     def _prep_inputs(self, x):
@@ -1119,15 +1168,7 @@ class Model(Layer):
         ctx = RunContext(True, dp, masks, self._train_params, self.name, row_map)
         ctx.capture = capture
         outs = self._forward(xs, ctx)
-        dps, stats = [], []
-        for p, t, kind, scale in zip(outs, ys, self._losses, self._loss_scales):
-            # keras: the loss is the mean over the output's columns, then over the batch -- the element-wise kernel over all B * n values,
-            # normalised by the global element count (n = 1: the (B, 1) heads as before)
-            n = p.numel() // B if B else 1
-            d, o = ops.loss(kind, p.reshape(B * n, 1), t.reshape(B * n, 1), B * world * n)
-            if scale != 1.0:
-                ops.axpy(d, d.clone(), scale - 1.0)
-            dps.append(d.reshape(p.shape)); stats.append(o)
+        dps, stats = self._loss_stats(outs, ys, B, world, True)
         for grp, a, b in segments(self._train_params):
             grp.grad[a:b].zero_()
         self._backward(dps, ctx)
@@ -1139,17 +1180,84 @@ class Model(Layer):
         self.optimizer.step()
         return stats
 
+    def _loss_stats(self, outs, ys, B, world, grad):
+        """Per output: the loss (with its gradient when `grad`) and the compiled metrics, all on the device.  Returns (gradients, the
+        (n_outputs, 2 + #loss-pass metrics) tensor [loss term, hits, metric, ...])."""
+        dps, stats = [], []
+        for p, t, kind, scale, w in zip(outs, ys, self._losses, self._loss_scales, self._loss_w):
+            # keras: the loss is the mean over the output's columns, then over the global batch.  The two losses of the first kernel keep it
+            # while the output is small (the element-wise kernel over all B * n values, normalised by the global element count: the bits every
+            # (B, 1) head always had); every other kind, every larger output and every evaluation is one ops.loss_pass over (B, n)
+            n = p.numel() // B if B else 1
+            p2, t2 = p.reshape(B, n), t.reshape(B, n)
+            if grad and kind in OLD_KERNEL_LOSSES and B * n < ops.LOSS_PASS_MIN_ELEMENTS:
+                d, o = ops.loss(kind, p.reshape(B * n, 1), t.reshape(B * n, 1), B * world * n)
+            else:
+                d, o = ops.loss_pass(kind, p2, t2, B * world, grad=grad)
+            if grad:
+                if scale * w != 1.0:
+                    ops.axpy(d, d.clone(), scale * w - 1.0)
+                dps.append(d.reshape(p.shape))
+            if self._metric_kinds:
+                o = torch.cat([o] + [ops.loss_pass(m, p2, t2, B * world, grad=False)[1][:1] for m in self._metric_kinds])
+            stats.append(o)
+        return dps, stats
+
+    def test_on_batch(self, x, y):
+        """keras test_on_batch: the inference-phase forward (as predict) and the compiled loss and metrics of it; no backward, no optimizer step.
+        Returns the list train_on_batch returns."""
+        xs = self._prep_inputs(x)
+        B = xs[0].shape[0]
+        return self.train_result(self.test_on_batch_device(xs, self._prep_targets(y, B)), B)
+
+    def test_on_batch_device(self, xs, ys):
+        """test_on_batch on device tensors without the device -> host read: the statistics tensor of train_on_batch_device."""
+        if self.optimizer is None:
+            raise RuntimeError('compile() the model before test_on_batch')
+        B = xs[0].shape[0]
+        dp = self.data_parallel
+        world = dp.world_size if dp is not None else 1
+        outs = self._forward(xs, RunContext(False))
+        stats = torch.stack(self._loss_stats(outs, ys, B, world, False)[1])
+        if dp is not None:
+            dp.all_reduce_sum(stats)
+        return stats
+
+    def evaluate(self, x, y, batch_size=32, verbose=0):
+        """keras evaluate: the mean of test_on_batch over chunks of batch_size rows, each weighted by its row count."""
+        if self.data_parallel is not None:
+            raise NotImplementedError('evaluate under data_parallel: call test_on_batch on each rank\'s rows')
+        xs = self._prep_inputs(x)
+        B = xs[0].shape[0]
+        ys = self._prep_targets(y, B)
+        tot = None
+        for s in range(0, B, batch_size):
+            nb = min(batch_size, B - s)
+            r = np.asarray(self.train_result(self.test_on_batch_device([t[s:s + nb] for t in xs], [t[s:s + nb] for t in ys]), nb)) * nb
+            tot = r if tot is None else tot + r
+        res = [float(v) / B for v in tot]
+        if verbose:
+            print(' - '.join('%s: %.6f' % (n, v) for n, v in zip(self.metrics_names, res)))
+        return res
+
+    def predict_on_batch(self, x):
+        """keras predict_on_batch: one inference-phase forward over all rows of x, no chunking."""
+        outs = [o.cpu().numpy() for o in self._forward(self._prep_inputs(x), RunContext(False))]
+        return outs if len(outs) > 1 else outs[0]
+
     def train_result(self, stats, B):
         """[loss, (per-output losses,) (accuracies)] as python floats, keras order, from train_on_batch_device's statistics (one device -> host read)."""
         world = self.data_parallel.world_size if self.data_parallel is not None else 1
         st = stats.cpu().numpy().astype(np.float64)
         losses = [float(v) * sc for v, sc in zip(st[:, 0], self._loss_scales)]
-        res = [float(sum(losses))]
+        res = [float(sum(l * w for l, w in zip(losses, self._loss_w)))]       # per-output entries stay unweighted, as keras reports them
         if len(losses) > 1:
             res += losses
-        if self.metrics:
-            cols = [int(np.prod(self.nodes[i].out_shape)) for i in self.output_ids]
-            res += [float(h) / (B * world * n) for h, n in zip(st[:, 1], cols)]
+        cols = [int(np.prod(self.nodes[i].out_shape)) for i in self.output_ids]
+        for row, n in zip(st, cols):
+            if self._acc:
+                res.append(float(row[1]) / (B * world * n))
+            res += [float(v) for v in row[2:]]
         return res
 
     def predict_device(self, x, batch_size=32):

@@ -10,6 +10,8 @@
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
+    from gennet_amd.keras.losses import logcosh, mean_absolute_error, mae, ...                # every name and alias of engine.LOSSES
+    from gennet_amd.keras.metrics import categorical_accuracy, mae, mse, mape, msle, cosine   # and their long names
 Every class executes on the HIP kernel library; see INTEGRATION.md.
 
 The sub-module tree of the import lines is a name space over gennet_amd.engine / gennet_amd.layers and nothing more, so it is built here,
@@ -62,6 +64,8 @@ _TREE = {
     'layers.convolutional': _conv,
     'layers.advanced_activations': _act,
     'layers.noise': _noise,
+    'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
+    'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }
 
 

@@ -728,6 +728,32 @@ def loss(kind, p, y, Bglobal=None):
     return dp, out
 
 
+LOSS_KINDS = {'binary_crossentropy': 0, 'mean_squared_error': 1, 'mean_absolute_error': 2, 'mean_absolute_percentage_error': 3,
+              'mean_squared_logarithmic_error': 4, 'hinge': 5, 'squared_hinge': 6, 'logcosh': 7, 'poisson': 8, 'kullback_leibler_divergence': 9,
+              'categorical_crossentropy': 10, 'cosine_proximity': 11, 'categorical_accuracy': 12}       # enum gn_loss
+LOSS_ALIASES = {'mse': 'mean_squared_error', 'mae': 'mean_absolute_error', 'mape': 'mean_absolute_percentage_error',
+                'msle': 'mean_squared_logarithmic_error', 'kld': 'kullback_leibler_divergence', 'cosine': 'cosine_proximity'}
+# element count from which the engine sends binary_crossentropy / mean_squared_error to loss_pass instead of the one-block kernel of loss():
+# the measured crossover (scripts/loss_bench.py) lies far below; the floor of 131 072 keeps every loss call of the
+# benchmark, the scripts and the older tests on the kernel, and the bits, it always had
+LOSS_PASS_MIN_ELEMENTS = 131072
+
+
+def loss_pass(kind, p, y, denom=None, grad=True, dp=None):
+    """gn_loss_pass: kind a name of LOSS_KINDS (or its integer); p, y (rows, cols) contiguous, any 4-byte alignment.  Returns (dp, out):
+    out[2] = [sum of the per-row terms / denom, #elements with round(p) == y], dp = d out[0] / dp (None with grad=False: only out is
+    written).  denom: the global row count (default rows).  dp: a tensor to write the gradient into instead of a new one."""
+    _chk(p, y, dp)
+    rows, cols = p.shape
+    if grad and dp is None:
+        dp = torch.empty_like(p)
+    out = torch.empty((2,), dtype=torch.float32, device=p.device)
+    ws = workspace(_lib.size('gn_loss_pass_workspace', rows, cols), p.device)
+    _lib.call('gn_loss_pass', LOSS_KINDS.get(kind, kind), _p(p), _p(y), _p(dp) if grad else None, _p(out), rows, cols, float(rows if denom is None else denom),
+              _p(ws), ws.numel(), _stream())
+    return (dp if grad else None), out
+
+
 def adam_step(p, g, m, v, lr_t, b1, b2, eps):
     """lr_t: a python float, or (inside a captured step graph) the integer device address of a float the host refreshes before every replay."""
     _chk(p, g, m, v)

@@ -304,6 +304,25 @@ int gn_bn_bwd_apply_conv1(const float* g, const float* w, int L, int Lout, int k
 int gn_bce_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream);
 int gn_mse_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream);
 
+/* ---- every Keras 2.2.4 loss / metric of compile(loss=, metrics=) as one streaming pass over a (rows, cols) output of any size
+ *      (gennet_amd/csrc/loss.hip; DESIGN.md section 8e lists the per-row terms and derivatives) -------------------------------
+ * out[0] = sum over the local rows of the per-row term / denom (denom: the GLOBAL row count, data-parallel ranks pass B * world);
+ * out[1] = #elements with round(p) == y.  dp (may be NULL: evaluation / metric form, only `out` is written) = d out[0] / dp, one
+ * store per element.  GN_LOSS_CATEGORICAL_ACCURACY: out[0] = #rows whose first arg-max of p is the first arg-max of y / denom, dp = 0.
+ * The grid scales with rows * cols; blocks write fp64 partials to `ws` (gn_loss_pass_workspace bytes, 8-byte aligned) with plain
+ * stores and a one-block kernel adds them in a fixed order: no atomics, the same bits on every run, a launch shape that depends on
+ * (rows, cols) only.  p, y, dp need 4-byte alignment only.  GN_EINVAL: unknown kind, rows < 1, cols < 1, denom < rows, a workspace
+ * that is too small, NULL p / y / out. */
+enum gn_loss {
+  GN_LOSS_BINARY_CROSSENTROPY = 0, GN_LOSS_MEAN_SQUARED_ERROR = 1, GN_LOSS_MEAN_ABSOLUTE_ERROR = 2, GN_LOSS_MEAN_ABSOLUTE_PERCENTAGE_ERROR = 3,
+  GN_LOSS_MEAN_SQUARED_LOGARITHMIC_ERROR = 4, GN_LOSS_HINGE = 5, GN_LOSS_SQUARED_HINGE = 6, GN_LOSS_LOGCOSH = 7, GN_LOSS_POISSON = 8,
+  GN_LOSS_KULLBACK_LEIBLER_DIVERGENCE = 9, GN_LOSS_CATEGORICAL_CROSSENTROPY = 10, GN_LOSS_COSINE_PROXIMITY = 11,
+  GN_LOSS_CATEGORICAL_ACCURACY = 12, GN_LOSS_KINDS = 13
+};
+size_t gn_loss_pass_workspace(long long rows, int cols);
+int gn_loss_pass(int kind, const float* p, const float* y, float* dp, float* out, long long rows, int cols, double denom,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Adam, keras form (bbhMahoGANy.py:1101,1107,1115,1119: Adam(lr=9e-5, beta_1=0.5)) ---------------------
  * m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (host). */
 int gn_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, void* stream);
