@@ -75,6 +75,8 @@ _SIGS = {
     'gn_bce_loss': [vp, vp, vp, vp, i32, i32, vp],
     'gn_mse_loss': [vp, vp, vp, vp, i32, i32, vp],
     'gn_loss_pass': [i32, vp, vp, vp, vp, i64, i32, f64, vp, sz, vp],
+    'gn_weight_count': [vp, i64, vp, vp, sz, vp],
+    'gn_loss_pass_weighted': [i32, vp, vp, vp, vp, vp, vp, i64, i32, vp, sz, vp],
     'gn_adam_step': [vp, vp, vp, vp, sz, f32, f32, f32, f32, vp],
     'gn_set_rng_base': [vp],
     'gn_adam_step_dyn': [vp, vp, vp, vp, sz, vp, f32, f32, f32, vp],
@@ -116,6 +118,8 @@ _SIZE_FNS = {
     'gn_conv1d_fwd_stats_workspace': [i32, i32, i32],
     'gn_optim_sumsq_slots': [sz],
     'gn_loss_pass_workspace': [i64, i32],
+    'gn_weight_count_workspace': [i64],
+    'gn_loss_pass_weighted_workspace': [i64, i32],
 }
 
 

@@ -88,7 +88,9 @@ def expected_collectives(nets, cnn_steps=2):
         if model is None or n == 0:
             continue
         parts[name + '_gradients'] = n * grad_bytes(model)
-        parts[name + '_loss_scalars'] = n * len(model.output_ids) * (2 + len(getattr(model, '_metric_kinds', ()))) * 4
+        wk = getattr(model, '_wmetric_kinds', ())      # weighted_metrics add [weighted hit share, weighted metric, ...] to every row
+        wcols = 1 + len(wk) if (getattr(model, '_wacc', False) or wk) else 0
+        parts[name + '_loss_scalars'] = n * len(model.output_ids) * (2 + len(getattr(model, '_metric_kinds', ())) + wcols) * 4
         bound = all(getattr(p, 'group', None) is not None for p in model._train_params)       # flat buffers exist after the first device step
         calls += n * ((len(segments(model._train_params)) if bound else 1) + 1)
     bns = [l for l in nets.generator.layers if isinstance(l, BatchNormalization)]

@@ -8,7 +8,7 @@ Mirrors the Keras 2.2.4 surface that BBH_version/bbhMahoGANy.py uses (SURVEY sec
   * compile(loss=, optimizer=Adam(lr=, beta_1=), metrics=['accuracy']) (:1101-1119); one optimizer state per compiled model
   * train_on_batch(x, y) -> [loss, *metrics] python floats, keras ordering for multi-output models (:1165, :1292, :1296)
   * every Keras loss name / alias / keras.losses callable, loss_weights=[...], several metrics; test_on_batch, evaluate, predict_on_batch
-    (ops.loss_pass)
+    (ops.loss_pass); sample_weight=, class_weight=, compile(weighted_metrics=) (ops.loss_pass_weighted; section 8f)
   * predict(x) -> ndarray | [ndarray] (default batch_size 32) (:1185, :1248, :1343); learning phase 1 in train_on_batch for
     the WHOLE graph, 0 in predict
   * save / save_weights / load_weights / load_model (:1135-1142, :1173, :1373-1375)
@@ -814,6 +814,8 @@ class Model(Layer):
         self.metrics = []
         self.loss_weights = None
         self._acc, self._metric_kinds = False, []
+        self.weighted_metrics = []
+        self._wacc, self._wmetric_kinds = False, []
         self._train_params = None
         self.data_parallel = None
         if inputs is not None:
@@ -1038,10 +1040,14 @@ class Model(Layer):
     # Model used as a layer inside another graph is expanded by _append, so forward/backward are never called on it.
 
     # -- keras training surface
-    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, data_parallel=None, **kwargs):
+    def compile(self, loss=None, optimizer=None, metrics=None, loss_weights=None, data_parallel=None, weighted_metrics=None, sample_weight_mode=None,
+                **kwargs):
         """Collects the trainable weights NOW (keras semantics): later changes of .trainable do not affect this model.
         loss: per output a name or alias of LOSSES, a keras.losses callable of the facade, or a callable squared error (K.lower_loss);
-        loss_weights: a list, one weight per output; metrics: any of ACC_METRICS / PASS_METRICS (names, aliases, facade callables)."""
+        loss_weights: a list, one weight per output; metrics: any of ACC_METRICS / PASS_METRICS (names, aliases, facade callables);
+        weighted_metrics: the same names, reported as sum_r w_r m_r / #{w != 0} under the sample weights of the call (ones without)."""
+        if sample_weight_mode is not None:
+            raise NotImplementedError('sample_weight_mode=%r: only per-sample weights (None), one weight per row' % (sample_weight_mode,))
         self.loss = loss
         n_out = len(self.output_ids)
         losses = list(loss) if isinstance(loss, (list, tuple)) else [loss] * n_out
@@ -1066,16 +1072,22 @@ class Model(Layer):
         self.loss_weights = None if loss_weights is None else [float(w) for w in loss_weights]
         self._loss_w = self.loss_weights or [1.0] * n_out
         self.metrics = list(metrics or [])
-        self._acc, self._metric_kinds = False, []     # the hit-count accuracy (one column, however often it is named) / the loss-pass metrics
-        for m in self.metrics:
-            name = _loss_name(m)
-            if not callable(m) and m in ACC_METRICS:
-                self._acc = True
-            elif name in PASS_METRICS:
-                if name not in self._metric_kinds:
-                    self._metric_kinds.append(name)
-            else:
-                raise NotImplementedError('metric %r: only %s and %s (or their aliases)' % (m, ACC_METRICS, PASS_METRICS))
+        self.weighted_metrics = list(weighted_metrics or [])
+
+        def kinds(ms):                                # the hit-count accuracy (one column, however often it is named) / the loss-pass metrics
+            acc, out = False, []
+            for m in ms:
+                name = _loss_name(m)
+                if not callable(m) and m in ACC_METRICS:
+                    acc = True
+                elif name in PASS_METRICS:
+                    if name not in out:
+                        out.append(name)
+                else:
+                    raise NotImplementedError('metric %r: only %s and %s (or their aliases)' % (m, ACC_METRICS, PASS_METRICS))
+            return acc, out
+        self._acc, self._metric_kinds = kinds(self.metrics)
+        self._wacc, self._wmetric_kinds = kinds(self.weighted_metrics)
         self.optimizer = _get_optimizer(optimizer)
         params, seen = [], set()
         if self.trainable:
@@ -1119,7 +1131,8 @@ class Model(Layer):
         if n_out > 1:
             names += ['out%d_loss' % k for k in range(n_out)]
         for k in range(n_out):
-            for m in (['acc'] if self._acc else []) + self._metric_kinds:
+            for m in ((['acc'] if self._acc else []) + self._metric_kinds
+                      + ['weighted_' + w for w in (['acc'] if self._wacc else []) + self._wmetric_kinds]):
                 names.append(m if n_out == 1 else 'out%d_%s' % (k, m))
         return names
 
@@ -1140,22 +1153,74 @@ class Model(Layer):
         assert len(ys) == n_out, 'model has %d outputs' % n_out
         return [to_device(a).reshape(B, -1) for a in ys]
 
-    def train_on_batch(self, x, y, dropout_masks=None, capture=None, row_map=None):
+    def _prep_weights(self, sample_weight, class_weight, y, B):
+        """keras' standardize_weights on the host: per output a float32 (B,) array or None (= ones); None when no output is weighted.
+        class_weight {class: weight} (single-output models) becomes the sample weights of the rows' classes: argmax of a row of y, or y[:, 0]
+        itself when y has one column.  Raises before anything is launched."""
+        n_out = len(self.output_ids)
+        if isinstance(sample_weight, dict):
+            raise NotImplementedError('sample_weight as a dict: pass a list, one entry (or None) per output')
+        if class_weight is not None and not isinstance(class_weight, dict):
+            raise ValueError('class_weight is a dict {class: weight}')
+        if class_weight is not None and n_out != 1:
+            raise ValueError('class_weight is supported for models with a single output only (this one has %d)' % n_out)
+        if sample_weight is not None:
+            if class_weight is not None:
+                import warnings
+                warnings.warn('both sample_weight and class_weight were given: class_weight is ignored', UserWarning)
+            if n_out == 1:
+                one = isinstance(sample_weight, (list, tuple)) and len(sample_weight) == 1 and np.ndim(sample_weight[0]) > 0
+                sws = [sample_weight[0] if one else sample_weight]
+            else:
+                if not isinstance(sample_weight, (list, tuple)) or len(sample_weight) != n_out:
+                    raise ValueError('sample_weight of a model with %d outputs is a list with one entry (or None) per output' % n_out)
+                sws = list(sample_weight)
+            out = []
+            for k, w in enumerate(sws):
+                if w is None:
+                    out.append(None)
+                    continue
+                w = np.asarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
+                if w.ndim != 1:
+                    raise ValueError('sample_weight of output %d has shape %s: one weight per row, a 1-D array, is expected' % (k, w.shape))
+                if w.shape[0] != B:
+                    raise ValueError('sample_weight of output %d has %d entries for %d rows' % (k, w.shape[0], B))
+                out.append(np.ascontiguousarray(w))
+            return out if any(w is not None for w in out) else None
+        if class_weight is None:
+            return None
+        y = np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y).reshape(B, -1)
+        cls = np.argmax(y, axis=1) if y.shape[1] > 1 else y[:, 0]
+        table = dict((float(k), float(v)) for k, v in class_weight.items())
+        missing = sorted(set(float(c) for c in cls) - set(table))
+        if missing:
+            raise ValueError('class_weight has no entry for the classes %s that y holds' % missing)
+        return [np.array([table[float(c)] for c in cls], dtype=np.float32)]
+
+    def train_on_batch(self, x, y, dropout_masks=None, capture=None, row_map=None, sample_weight=None, class_weight=None):
         """One optimizer step.  Returns [loss, (per-output losses,) (accuracies)] as python floats, keras order.
+        sample_weight: one weight per row (a list with one entry or None per output on multi-output models); class_weight: {class: weight},
+        single-output models.  The loss is sum_r w_r l_r / #{w != 0} over the GLOBAL batch, as Keras 2.2.4.
         `dropout_masks` ({dropout layer name: uint8 keep mask}) is a testing hook that replaces the Philox draws; `capture` (a dict) is
         another: it receives {layer name: output tensor} of every executed layer (outputs include the fused activation / dropout).
         row_map (data parallelism): ([(global_row_start, n_rows), ...], global_rows) when the local rows are not the rank's contiguous slice
         [rank * B, (rank + 1) * B) of the global batch (the default) -- the discriminator batch of bbh.gan_train_step."""
         xs = self._prep_inputs(x)
         B = xs[0].shape[0]
+        sws = self._weights_to_device(self._prep_weights(sample_weight, class_weight, y, B))
         ys = self._prep_targets(y, B)
-        stats = self.train_on_batch_device(xs, ys, dropout_masks, capture, row_map)
+        stats = self.train_on_batch_device(xs, ys, dropout_masks, capture, row_map, sws)
         return self.train_result(stats, B)
 
-    def train_on_batch_device(self, xs, ys, dropout_masks=None, capture=None, row_map=None):
+    @staticmethod
+    def _weights_to_device(sws):
+        return None if sws is None else [None if w is None else to_device(w) for w in sws]
+
+    def train_on_batch_device(self, xs, ys, dropout_masks=None, capture=None, row_map=None, sample_weights=None):
         """train_on_batch on device tensors (inputs as the graph takes them, targets (B, 1)) without the final device -> host read: returns
         the (n_outputs, 2) device tensor [summed loss term, metric hits] that train_result turns into keras' list.  No host synchronisation
-        anywhere in it, so the whole step can be captured into a hipGraph (engine.StepGraph)."""
+        anywhere in it, so the whole step can be captured into a hipGraph (engine.StepGraph).  sample_weights: per output a (B,) device tensor
+        or None; their non-zero count stays on the device, so a captured step replays with whatever the tensors hold then."""
         if self.optimizer is None:
             raise RuntimeError('compile() the model before train_on_batch')
         self._ensure_bound()
@@ -1168,7 +1233,7 @@ class Model(Layer):
         ctx = RunContext(True, dp, masks, self._train_params, self.name, row_map)
         ctx.capture = capture
         outs = self._forward(xs, ctx)
-        dps, stats = self._loss_stats(outs, ys, B, world, True)
+        dps, stats = self._loss_stats(outs, ys, B, world, True, sample_weights)
         for grp, a, b in segments(self._train_params):
             grp.grad[a:b].zero_()
         self._backward(dps, ctx)
@@ -1180,11 +1245,43 @@ class Model(Layer):
         self.optimizer.step()
         return stats
 
-    def _loss_stats(self, outs, ys, B, world, grad):
+    def _loss_stats(self, outs, ys, B, world, grad, sws=None):
         """Per output: the loss (with its gradient when `grad`) and the compiled metrics, all on the device.  Returns (gradients, the
-        (n_outputs, 2 + #loss-pass metrics) tensor [loss term, hits, metric, ...])."""
+        (n_outputs, 2 + #loss-pass metrics) tensor [loss term, hits, metric, ...]; with weighted_metrics compiled the rows go on with
+        [weighted hit share, weighted metric, ...]).
+        sws: per output a (B,) weight tensor of the LOCAL rows or None (ones).  A weighted output always takes ops.loss_pass_weighted (the
+        one-block kernels have no weighted form), normalised by the number of non-zero weights of the GLOBAL batch: every weighted output's
+        count is taken first and all of them cross the ranks in ONE all-reduce."""
         dps, stats = [], []
-        for p, t, kind, scale, w in zip(outs, ys, self._losses, self._loss_scales, self._loss_w):
+        sws = list(sws) if sws is not None else [None] * len(outs)
+        if len(sws) != len(outs):
+            raise ValueError('%d sample weight entries for %d outputs' % (len(sws), len(outs)))
+        for k, sw in enumerate(sws):
+            if sw is not None and (tuple(sw.shape) != (B,) or sw.dtype != torch.float32):
+                raise ValueError('sample weights of output %d: a float32 tensor of shape (%d,) is expected, got %s %s' % (k, B, tuple(sw.shape), sw.dtype))
+        weighted = [k for k, sw in enumerate(sws) if sw is not None]
+        counts = None
+        if weighted:
+            counts = torch.empty((len(weighted),), dtype=torch.float64, device=outs[0].device)
+            for j, k in enumerate(weighted):
+                ops.weight_count(sws[k], counts[j:j + 1])
+            if self.data_parallel is not None:
+                self.data_parallel.all_reduce_sum(counts)
+        wcols = self._wacc or bool(self._wmetric_kinds)
+        for k, (p, t, kind, scale, w) in enumerate(zip(outs, ys, self._losses, self._loss_scales, self._loss_w)):
+            if sws[k] is not None:
+                n = p.numel() // B
+                p2, t2, cnt = p.reshape(B, n), t.reshape(B, n), counts[weighted.index(k):weighted.index(k) + 1]
+                d, o = ops.loss_pass_weighted(kind, p2, t2, sws[k], cnt, grad=grad)
+                if grad:
+                    if scale * w != 1.0:
+                        ops.axpy(d, d.clone(), scale * w - 1.0)
+                    dps.append(d.reshape(p.shape))
+                cols = [o[:2]] + [ops.loss_pass(m, p2, t2, B * world, grad=False)[1][:1] for m in self._metric_kinds]     # metrics= stay unweighted
+                if wcols:
+                    cols += [o[2:]] + [ops.loss_pass_weighted(m, p2, t2, sws[k], cnt, grad=False)[1][:1] for m in self._wmetric_kinds]
+                stats.append(torch.cat(cols) if len(cols) > 1 else cols[0])
+                continue
             # keras: the loss is the mean over the output's columns, then over the global batch.  The two losses of the first kernel keep it
             # while the output is small (the element-wise kernel over all B * n values, normalised by the global element count: the bits every
             # (B, 1) head always had); every other kind, every larger output and every evaluation is one ops.loss_pass over (B, n)
@@ -1198,19 +1295,25 @@ class Model(Layer):
                 if scale * w != 1.0:
                     ops.axpy(d, d.clone(), scale * w - 1.0)
                 dps.append(d.reshape(p.shape))
-            if self._metric_kinds:
-                o = torch.cat([o] + [ops.loss_pass(m, p2, t2, B * world, grad=False)[1][:1] for m in self._metric_kinds])
+            if self._metric_kinds or wcols:
+                ms = dict((m, ops.loss_pass(m, p2, t2, B * world, grad=False)[1][:1])
+                          for m in self._metric_kinds + [m for m in self._wmetric_kinds if m not in self._metric_kinds])
+                cols = [o] + [ms[m] for m in self._metric_kinds]
+                if wcols:                  # weights of ones: every weighted metric is the plain one, the hit share hits / (B world n)
+                    cols += [o[1:2] * (1.0 / (B * world * n))] + [ms[m] for m in self._wmetric_kinds]
+                o = torch.cat(cols)
             stats.append(o)
         return dps, stats
 
-    def test_on_batch(self, x, y):
+    def test_on_batch(self, x, y, sample_weight=None):
         """keras test_on_batch: the inference-phase forward (as predict) and the compiled loss and metrics of it; no backward, no optimizer step.
         Returns the list train_on_batch returns."""
         xs = self._prep_inputs(x)
         B = xs[0].shape[0]
-        return self.train_result(self.test_on_batch_device(xs, self._prep_targets(y, B)), B)
+        sws = self._weights_to_device(self._prep_weights(sample_weight, None, y, B))
+        return self.train_result(self.test_on_batch_device(xs, self._prep_targets(y, B), sws), B)
 
-    def test_on_batch_device(self, xs, ys):
+    def test_on_batch_device(self, xs, ys, sample_weights=None):
         """test_on_batch on device tensors without the device -> host read: the statistics tensor of train_on_batch_device."""
         if self.optimizer is None:
             raise RuntimeError('compile() the model before test_on_batch')
@@ -1218,22 +1321,25 @@ class Model(Layer):
         dp = self.data_parallel
         world = dp.world_size if dp is not None else 1
         outs = self._forward(xs, RunContext(False))
-        stats = torch.stack(self._loss_stats(outs, ys, B, world, False)[1])
+        stats = torch.stack(self._loss_stats(outs, ys, B, world, False, sample_weights)[1])
         if dp is not None:
             dp.all_reduce_sum(stats)
         return stats
 
-    def evaluate(self, x, y, batch_size=32, verbose=0):
-        """keras evaluate: the mean of test_on_batch over chunks of batch_size rows, each weighted by its row count."""
+    def evaluate(self, x, y, batch_size=32, verbose=0, sample_weight=None):
+        """keras evaluate: the mean of test_on_batch over chunks of batch_size rows, each weighted by its row count.  With sample_weight every
+        chunk is normalised by its OWN count of non-zero weights (keras' test_loop)."""
         if self.data_parallel is not None:
             raise NotImplementedError('evaluate under data_parallel: call test_on_batch on each rank\'s rows')
         xs = self._prep_inputs(x)
         B = xs[0].shape[0]
+        sws = self._weights_to_device(self._prep_weights(sample_weight, None, y, B))
         ys = self._prep_targets(y, B)
         tot = None
         for s in range(0, B, batch_size):
             nb = min(batch_size, B - s)
-            r = np.asarray(self.train_result(self.test_on_batch_device([t[s:s + nb] for t in xs], [t[s:s + nb] for t in ys]), nb)) * nb
+            sw = None if sws is None else [None if w is None else w[s:s + nb] for w in sws]
+            r = np.asarray(self.train_result(self.test_on_batch_device([t[s:s + nb] for t in xs], [t[s:s + nb] for t in ys], sw), nb)) * nb
             tot = r if tot is None else tot + r
         res = [float(v) / B for v in tot]
         if verbose:
@@ -1254,10 +1360,14 @@ class Model(Layer):
         if len(losses) > 1:
             res += losses
         cols = [int(np.prod(self.nodes[i].out_shape)) for i in self.output_ids]
+        nm = 2 + len(self._metric_kinds)              # then, with weighted_metrics compiled: [weighted hit share, weighted metric, ...]
         for row, n in zip(st, cols):
             if self._acc:
                 res.append(float(row[1]) / (B * world * n))
-            res += [float(v) for v in row[2:]]
+            res += [float(v) for v in row[2:nm]]
+            if self._wacc:
+                res.append(float(row[nm]))
+            res += [float(v) for v in row[nm + 1:]]
         return res
 
     def predict_device(self, x, batch_size=32):
@@ -1280,12 +1390,17 @@ class Model(Layer):
             return [o.cpu().numpy() for o in out]
         return out.cpu().numpy()
 
-    def fit(self, x, y, batch_size=32, epochs=1, verbose=0, shuffle=True, **kwargs):
-        """Minimal keras fit: epochs of shuffled mini-batches through train_on_batch; returns {'loss': [...]}."""
+    def fit(self, x, y, batch_size=32, epochs=1, verbose=0, shuffle=True, sample_weight=None, class_weight=None, validation_data=None, **kwargs):
+        """Minimal keras fit: epochs of shuffled mini-batches through train_on_batch; returns {'loss': [...]}.  sample_weight / class_weight
+        are shuffled with the rows.  validation_data (x, y) or (x, y, sample_weight) is evaluated after every epoch and adds 'val_loss' and
+        one 'val_<name>' per compiled metric to the history."""
         x = np.asarray(x)
         n = x.shape[0]
         ys = list(y) if (isinstance(y, (list, tuple)) and len(self.output_ids) > 1) else [y]
         ys = [np.asarray(a) for a in ys]
+        sws = self._prep_weights(sample_weight, class_weight, ys[0], n)
+        if validation_data is not None and len(validation_data) not in (2, 3):
+            raise ValueError('validation_data is (x, y) or (x, y, sample_weight)')
         hist = {'loss': []}
         rng = np.random.RandomState(0)
         for ep in range(epochs):
@@ -1294,11 +1409,18 @@ class Model(Layer):
             for s in range(0, n, batch_size):
                 idx = order[s:s + batch_size]
                 yy = [a[idx] for a in ys]
-                r = self.train_on_batch(x[idx], yy if len(yy) > 1 else yy[0])
+                sw = None if sws is None else [None if w is None else w[idx] for w in sws]
+                r = self.train_on_batch(x[idx], yy if len(yy) > 1 else yy[0], sample_weight=sw if sw is None or len(sw) > 1 else sw[0])
                 tot += r[0] * len(idx); cnt += len(idx)
             hist['loss'].append(tot / max(cnt, 1))
+            if validation_data is not None:
+                val = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size,
+                                    sample_weight=validation_data[2] if len(validation_data) == 3 else None)
+                for name, v in zip(self.metrics_names, val):
+                    hist.setdefault('val_' + name, []).append(v)
             if verbose:
-                print('Epoch %d/%d - loss: %.6f' % (ep + 1, epochs, hist['loss'][-1]))
+                print('Epoch %d/%d - loss: %.6f' % (ep + 1, epochs, hist['loss'][-1])
+                      + (' - val_loss: %.6f' % hist['val_loss'][-1] if validation_data is not None else ''))
         return hist
 
     def summary(self, print_fn=None):

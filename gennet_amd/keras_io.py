@@ -445,10 +445,13 @@ def save_model(model, path, include_optimizer=True, writer=None):
     save_weights_to_group(w.root.create_group('model_weights'), top_layers(model))
     opt = model.optimizer
     if include_optimizer and opt is not None:
-        w.root.attrs['training_config'] = json.dumps({
+        tc = {
             'optimizer_config': {'class_name': type(opt).__name__, 'config': opt.get_config()},
             'loss': _loss_json(model.loss), 'metrics': _loss_json(list(model.metrics or [])), 'sample_weight_mode': None,
-            'loss_weights': getattr(model, 'loss_weights', None)}).encode('utf-8')
+            'loss_weights': getattr(model, 'loss_weights', None)}
+        if getattr(model, 'weighted_metrics', None):  # only then: every file of a model compiled without them keeps its bytes
+            tc['weighted_metrics'] = _loss_json(list(model.weighted_metrics))
+        w.root.attrs['training_config'] = json.dumps(tc).encode('utf-8')
         if opt.state is not None and model._train_params:
             # keras: optimizer.weights in model.trainable_weights order -- [iterations] (if the class saves it) + one block per state array;
             # names in the scheme of a first compile, training/<Class>/Variable[_k]:0 (readers go by the weight_names order, never by name)
@@ -480,7 +483,7 @@ def load_model(path, custom_objects=None, compile=True):
         # any of engine.OPTIMIZERS with its own config, clipnorm / clipvalue included.  RMSprop, Adagrad and Adadelta files carry no iteration
         # count (Keras 2.2.4 does not save it): a resumed run restarts at iterations = 0, and with decay > 0 restarts the decay schedule
         model.compile(loss=tc['loss'], optimizer=optimizer_from_config(tc['optimizer_config']), metrics=tc.get('metrics') or [],
-                      loss_weights=tc.get('loss_weights'))
+                      loss_weights=tc.get('loss_weights'), **({'weighted_metrics': tc['weighted_metrics']} if tc.get('weighted_metrics') else {}))
         if 'optimizer_weights' in f:
             og = f['optimizer_weights']
             names = _decode_list(og.attrs.get('weight_names'))

@@ -754,6 +754,36 @@ def loss_pass(kind, p, y, denom=None, grad=True, dp=None):
     return (dp if grad else None), out
 
 
+def weight_count(w, count=None):
+    """gn_weight_count: the number of w[r] != 0 of a (rows,) weight vector as a one-element fp64 device tensor (exact; it never visits the
+    host).  Data-parallel ranks all-reduce it before loss_pass_weighted reads it.  count: a tensor (or one-element view) to write into."""
+    _chk(w, count)
+    if count is None:
+        count = torch.empty((1,), dtype=torch.float64, device=w.device)
+    ws = workspace(_lib.size('gn_weight_count_workspace', w.numel()), w.device)
+    _lib.call('gn_weight_count', _p(w), w.numel(), _p(count), _p(ws), ws.numel(), _stream())
+    return count
+
+
+def loss_pass_weighted(kind, p, y, w, count, grad=True, dp=None):
+    """gn_loss_pass_weighted: loss_pass with one weight per row (w: (rows,) fp32) and the normaliser `count` read on the device (a one-element
+    fp64 tensor: weight_count(w), summed over the ranks).  Returns (dp, out): out[3] = [sum_r w_r term_r / count, #elements with
+    round(p) == y, sum_r w_r hits_r / (count cols)], dp = d out[0] / dp (None with grad=False)."""
+    _chk(p, y, w, count, dp)
+    rows, cols = p.shape
+    if w.numel() != rows or w.dtype != torch.float32:
+        raise ValueError('loss_pass_weighted: %d float32 weights expected, got %s %s' % (rows, tuple(w.shape), w.dtype))
+    if count.numel() != 1 or count.dtype != torch.float64:
+        raise ValueError('loss_pass_weighted: count is one float64 value on the device')
+    if grad and dp is None:
+        dp = torch.empty_like(p)
+    out = torch.empty((3,), dtype=torch.float32, device=p.device)
+    ws = workspace(_lib.size('gn_loss_pass_weighted_workspace', rows, cols), p.device)
+    _lib.call('gn_loss_pass_weighted', LOSS_KINDS.get(kind, kind), _p(p), _p(y), _p(w), _p(count), _p(dp) if grad else None, _p(out), rows, cols,
+              _p(ws), ws.numel(), _stream())
+    return (dp if grad else None), out
+
+
 def adam_step(p, g, m, v, lr_t, b1, b2, eps):
     """lr_t: a python float, or (inside a captured step graph) the integer device address of a float the host refreshes before every replay."""
     _chk(p, g, m, v)

@@ -323,6 +323,24 @@ size_t gn_loss_pass_workspace(long long rows, int cols);
 int gn_loss_pass(int kind, const float* p, const float* y, float* dp, float* out, long long rows, int cols, double denom,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the weighted form of the pass: Keras' sample_weight / class_weight / weighted_metrics ----------
+ * w: one float per local row.  count: ONE double in device memory, the number of non-zero weights of the GLOBAL batch, read by the
+ * kernels (never by the host): gn_weight_count writes the local count, data-parallel ranks all-reduce it before the pass, and a
+ * captured step replays with new weights.  gn_weight_count: exact, fixed-order, no atomics, a launch shape that depends on `rows`
+ * only; its workspace holds gn_weight_count_workspace(rows) bytes, 8-byte aligned.
+ * gn_loss_pass_weighted, out[3]: out[0] = sum over the local rows of w_r * (per-row term) / count; out[1] = #elements with
+ * round(p) == y (unweighted, as gn_loss_pass); out[2] = sum over the local rows of w_r * (the row's hits) / (count * cols).
+ * dp (may be NULL, the same `out` bits) = d out[0] / dp, one store per element, rows of weight zero included (+-0).  Negative
+ * weights count as non-zero; count == 0 gives 0 / 0 = NaN, as Keras does.  Everything else as gn_loss_pass: fp64 terms on the fp32
+ * inputs, one rounding, fp64 partials in `ws` (gn_loss_pass_weighted_workspace bytes, 8-byte aligned), the same bits on every run, a
+ * grid that depends on (rows, cols) only; p, y, w, dp need 4-byte alignment only.  GN_EINVAL: unknown kind, rows < 1, cols < 1, a
+ * workspace that is too small or misaligned, NULL p / y / w / count / out. */
+size_t gn_weight_count_workspace(long long rows);
+int gn_weight_count(const float* w, long long rows, double* count, void* ws, size_t ws_bytes, void* stream);
+size_t gn_loss_pass_weighted_workspace(long long rows, int cols);
+int gn_loss_pass_weighted(int kind, const float* p, const float* y, const float* w, const double* count, float* dp, float* out,
+                          long long rows, int cols, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Adam, keras form (bbhMahoGANy.py:1101,1107,1115,1119: Adam(lr=9e-5, beta_1=0.5)) ---------------------
  * m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (host). */
 int gn_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, void* stream);
