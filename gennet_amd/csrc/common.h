@@ -36,6 +36,8 @@ const Switches& switches();
 const uint64_t* rng_base();
 void prof_begin(hipStream_t s);
 void prof_end(hipStream_t s, double flop, int kind, double bytes = 0.0);  // kind 0: conv_mfma (fwd, dgrad), 1: wgrad_mfma, 2: bf16x3 conv, 3: fused synthesiser, 4: fused noise chain, 5: transform-domain conv F(2,5) (flop = executed = 0.6 algorithmic), 6: transform-domain wgrad, 7: transform-domain stride-2 conv (0.7), 8: transform-domain stride-2 wgrad (0.7), 9: anyc conv (forward, data gradient, each phase of a strided one), 10: anyc wgrad
+// small_conv.hip, one kind per kernel (flop = 2 B M ntaps Cin Cout): 11: conv_smallcin, 12: conv_smallcout, 13: conv_cout1_rows, 14: wgrad_smallcin_tab,
+// 15: wgrad_small (small Cout, stride > 1), 16: wgrad_smallcout_s1, 17: sum_partials_l1 (level 1 of the two-level reduce; flop = its additions)
 
 
 // ---------------------------------------------------------------------------------------------

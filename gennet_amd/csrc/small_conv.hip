@@ -10,6 +10,8 @@
 
 namespace gn {
 
+// launch counters (prof_end kinds 11..17): which small-channel kernel a call reached; 2 B M ntaps Cin Cout flop per launch
+static double small_conv_flop(int B, int M, int ntaps, int Cin, int Cout) { return 2.0 * B * (double)M * ntaps * Cin * Cout; }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -109,12 +111,14 @@ int conv_smallcin_dispatch(const ConvArgs& a, hipStream_t s) {
   const int m_tiles = cdiv(a.M, MT);
   const unsigned grid = (unsigned)m_tiles * a.B;
   if (grid == 0) return GN_OK;
+  prof_begin(s);
   switch (a.Cin) {
     case 1: hipLaunchKernelGGL(conv_smallcin_kernel<1>, dim3(grid), dim3(256), 0, s, a, m_tiles, MT); break;
     case 2: hipLaunchKernelGGL(conv_smallcin_kernel<2>, dim3(grid), dim3(256), 0, s, a, m_tiles, MT); break;
     case 3: hipLaunchKernelGGL(conv_smallcin_kernel<3>, dim3(grid), dim3(256), 0, s, a, m_tiles, MT); break;
     default: hipLaunchKernelGGL(conv_smallcin_kernel<4>, dim3(grid), dim3(256), 0, s, a, m_tiles, MT); break;
   }
+  prof_end(s, small_conv_flop(a.B, a.M, a.t.ntaps, a.Cin, a.Cout), 11);
   return check_launch("conv_smallcin");
 }
 
@@ -223,16 +227,20 @@ int conv_smallcout_dispatch(const ConvArgs& a, hipStream_t s) {
   if (a.Cout == 1 && contiguous && a.Cin >= 256) {
     constexpr int ROWS = 16;
     const int runs_per_b = cdiv(a.M, ROWS);
+    prof_begin(s);
     hipLaunchKernelGGL((conv_cout1_rows_kernel<5, ROWS>), dim3(cdiv((size_t)a.B * runs_per_b, 4)), dim3(256), 0, s, a, runs_per_b);
+    prof_end(s, small_conv_flop(a.B, a.M, a.t.ntaps, a.Cin, a.Cout), 13);
     return check_launch("conv_cout1_rows");
   }
   const unsigned grid = cdiv(rows, 4);
+  prof_begin(s);
   switch (a.Cout) {
     case 1: hipLaunchKernelGGL(conv_smallcout_kernel<1>, dim3(grid), dim3(256), 0, s, a); break;
     case 2: hipLaunchKernelGGL(conv_smallcout_kernel<2>, dim3(grid), dim3(256), 0, s, a); break;
     case 3: hipLaunchKernelGGL(conv_smallcout_kernel<3>, dim3(grid), dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(conv_smallcout_kernel<4>, dim3(grid), dim3(256), 0, s, a); break;
   }
+  prof_end(s, small_conv_flop(a.B, a.M, a.t.ntaps, a.Cin, a.Cout), 12);
   return check_launch("conv_smallcout");
 }
 
@@ -541,7 +549,9 @@ __global__ void sum_partials_kernel(const float* __restrict__ part, float* __res
 
 static int sum_partials(float* part, float* out, size_t n, int chunks, hipStream_t s) {
   if (chunks > 2 * SUM_GROUPS) {
+    prof_begin(s);
     hipLaunchKernelGGL(sum_partials_l1_kernel, dim3(cdiv(n, 256), SUM_GROUPS), dim3(256), 0, s, part, n, chunks);
+    prof_end(s, (double)n * (chunks - SUM_GROUPS), 17);
     int rc = check_launch("sum_partials_l1");
     if (rc) return rc;
     chunks = SUM_GROUPS;
@@ -568,12 +578,14 @@ int wgrad_small_dispatch(WgradSmallArgs a, float* dw, size_t ws_bytes, hipStream
   dim3 grid((NQ + NQc - 1) / NQc, chunks);
   if (!small_in && a.in_stride == 1) {   // every x row loaded once
     a.rows_per_chunk = (int)(((size_t)a.B * a.Lin + chunks - 1) / chunks);
+    prof_begin(s);
     switch (CS) {
       case 1: hipLaunchKernelGGL(wgrad_smallcout_s1_kernel<1>, grid, dim3(256), 0, s, a); break;
       case 2: hipLaunchKernelGGL(wgrad_smallcout_s1_kernel<2>, grid, dim3(256), 0, s, a); break;
       case 3: hipLaunchKernelGGL(wgrad_smallcout_s1_kernel<3>, grid, dim3(256), 0, s, a); break;
       default: hipLaunchKernelGGL(wgrad_smallcout_s1_kernel<4>, grid, dim3(256), 0, s, a); break;
     }
+    prof_end(s, small_conv_flop(a.B, a.M, a.ntaps, a.Cin, a.Cout), 16);
     int rc1 = check_launch("wgrad_smallcout_s1");
     if (rc1) return rc1;
     const size_t n1 = (size_t)a.ntaps * a.Cin * a.Cout;
@@ -582,6 +594,7 @@ int wgrad_small_dispatch(WgradSmallArgs a, float* dw, size_t ws_bytes, hipStream
 #define GN_WS(CSV)                                                                                            \
   if (small_in) hipLaunchKernelGGL((wgrad_smallcin_tab_kernel<CSV>), grid, dim3(256), 0, s, a);               \
   else hipLaunchKernelGGL((wgrad_small_kernel<CSV, false>), grid, dim3(256), 0, s, a);
+  prof_begin(s);
   switch (CS) {
     case 1: GN_WS(1); break;
     case 2: GN_WS(2); break;
@@ -589,6 +602,7 @@ int wgrad_small_dispatch(WgradSmallArgs a, float* dw, size_t ws_bytes, hipStream
     default: GN_WS(4); break;
   }
 #undef GN_WS
+  prof_end(s, small_conv_flop(a.B, a.M, a.ntaps, a.Cin, a.Cout), small_in ? 14 : 15);
   int rc = check_launch("wgrad_small");
   if (rc) return rc;
   const size_t n = (size_t)a.ntaps * a.Cin * a.Cout;

@@ -852,7 +852,10 @@ def prof_reset():
 
 def prof_collect(kind=-1):
     """kind 0: conv_mfma kernels (forward + data gradient), 1: wgrad_mfma_kernel, 2: bf16x3 conv (opt-in), 3: fused synthesiser,
-    9: anyc forward-form launches (forward, data gradient, each phase of a strided one), 10: anyc weight gradient, -1: all."""
+    9: anyc forward-form launches (forward, data gradient, each phase of a strided one), 10: anyc weight gradient,
+    11 .. 17: the small-channel kernels of csrc/small_conv.hip, one kind each -- 11: conv_smallcin (Cin <= 4), 12: conv_smallcout (Cout <= 4),
+    13: conv_cout1_rows (Cout 1, Cin >= 256, 5 contiguous taps, unit strides), 14: wgrad_smallcin_tab, 15: wgrad_small (small Cout, stride > 1),
+    16: wgrad_smallcout_s1 (small Cout, stride 1), 17: level 1 of the two-level partial-slab reduce (more than 64 chunks), -1: all."""
     import ctypes
     out = (ctypes.c_double * 4)()
     _lib.call('gn_prof_collect', int(kind), ctypes.cast(out, ctypes.c_void_p))

@@ -392,7 +392,8 @@ int gn_bn_finalize_zero_debias_dyn(const double* sums, double count, const float
 int gn_prof_enable(int on);
 int gn_prof_reset(void);
 /* sums over launches since reset of one kernel family (kind 0 = conv_mfma_kernel: forward + data gradient,
- * 1 = wgrad_mfma_kernel, 9 = the anyc conv, 10 = the anyc weight gradient, -1 = all): out[0] = launches, out[1] = total ms, out[2] = total algorithmic FLOP,
+ * 1 = wgrad_mfma_kernel, 9 = the anyc conv, 10 = the anyc weight gradient, 11 .. 17 = the small-channel
+ * kernels of small_conv.hip, one kind each, -1 = all): out[0] = launches, out[1] = total ms, out[2] = total algorithmic FLOP,
  * out[3] = total algorithmic bytes (each operand read once, the result written once) */
 int gn_prof_collect(int kind, double* out4_host);
 

@@ -138,7 +138,7 @@ def test_any_channel_pairs_parity_bounds_determinism_and_family(B, L, Cin, Cout,
     from gennet_amd import _lib, ops
     fwd_any, dgrad_any = ops.conv_needs_any(Cin, Cout), ops.conv_needs_any(Cout, Cin)     # the data gradient runs the swapped pair
     assert fwd_any or dgrad_any
-    fwd_kinds, wgrad_kinds = ({9: 1}, {10: 1}) if fwd_any else ({}, {})                   # (the small-channel kernels have no counter)
+    fwd_kinds, wgrad_kinds = ({9: 1}, {10: 1}) if fwd_any else ({}, {})                   # (the small-channel kernels are counted apart: conv_family.SMALL_KINDS)
     rng = np.random.RandomState(B * 1000 + L + Cin * 7 + Cout)
     Lout, pl = geometry(L, k, s, padding)
     assert (Lout, pl) == tuple(ops.conv_geometry(L, k, s, padding))
@@ -236,7 +236,7 @@ def test_aligned_shapes_reach_the_same_kernels_with_the_same_bits():
                 for p, q in zip(strict, anyc):
                     assert torch.equal(p, q), (name, B, L, Cin, Cout, k, s, math)
                 seen |= set(n_any)
-    assert seen >= {0, 1, 5, 6, 7, 8}, seen          # the table reached every counted family (the small kernels have no counter)
+    assert seen >= {0, 1, 5, 6, 7, 8}, seen          # the table reached every counted family (the small kernels are counted apart: conv_family.SMALL_KINDS, tests/test_small_conv_gpu.py)
 
 
 def test_predicate_is_what_the_strict_dispatchers_refuse():

@@ -179,7 +179,7 @@ def test_dense_any_shape_gemm(B, n_in, n_out):
 @pytest.mark.parametrize("B,n_in,n_out", [(1, 4, 8), (33, 8, 12), (17, 100, 36)])
 def test_dense_matrix_core_route_at_its_smallest_widths(B, n_in, n_out):
     """Aligned widths beyond the heads go to the MFMA conv kernels as a 1-tap conv (launch counter 0: conv, 1: weight gradient); the data
-    gradient is the conv with the widths swapped, so with in <= 4 it is a small-channel launch (no counter)."""
+    gradient is the conv with the widths swapped, so with in <= 4 it is a small-channel launch (counted apart: conv_family.SMALL_KINDS)."""
     from gennet_amd import ops
     rng = np.random.RandomState(B + n_in + n_out)
     x = f32(rng.uniform(-1, 1, (B, n_in))); w = f32(rng.randn(n_in, n_out) * 0.3); b = f32(rng.randn(n_out))
