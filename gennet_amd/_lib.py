@@ -1,10 +1,13 @@
-"""ctypes binding of libgennet_hip.so (C ABI: include/gennet_hip.h).
+"""ctypes binding of libgennet_hip.so, derived from the one declaration of its C ABI: include/gennet_hip.h.
 
 The HIP library is the product path: if it is missing this module raises at import of the first op -- there is
 no CPU / eager-PyTorch fallback anywhere in gennet_amd.
 """
 import ctypes as C
 import os
+import re
+
+from . import build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libgennet_hip.so')
@@ -13,123 +16,61 @@ _lib = None
 
 vp, i32, i64, f32, f64, u64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_uint64, C.c_size_t
 
-_SIGS = {
-    'gn_conv1d_fwd': [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-    'gn_conv1d_fwd_bf16x3': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp],
-    'gn_conv1d_fwd_wino': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-    'gn_conv1d_fwd_stats': [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_fwd_dropout': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp],
-    'gn_conv1d_fwd_any': [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-    'gn_conv1d_dgrad_any': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_wgrad_any': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_transpose_w': [vp, vp, i32, i32, i32, vp],
-    'gn_conv1d_dgrad': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_dgrad_fused': [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp],
-    'gn_dense_bwd_fused': [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, f32, f32, vp],
-    'gn_conv1d_wgrad': [vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    'gn_conv2d_w2_fold': [vp, vp, vp, vp, i32, i32, i32, vp],
-    'gn_conv2d_w2_unfold_grad': [vp, vp, vp, vp, i32, i32, i32, vp],
-    'gn_conv1d_tapfold_x': [vp, vp, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_tapunfold_dx': [vp, vp, i32, i32, i32, i32, i32, vp],
-    'gn_conv1d_tapfold_w': [vp, vp, i32, i32, i32, vp],
-    'gn_conv1d_tapunfold_dw': [vp, vp, i32, i32, i32, vp],
-    'gn_conv1d_tap_groups': [i32, vp, vp],
-    'gn_conv1d_up2_fold': [vp, vp, vp, vp, i32, i32, i32, vp],
-    'gn_conv1d_up2_unfold_grad': [vp, vp, vp, vp, i32, i32, i32, vp],
-    'gn_dense_fwd': [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
-    'gn_dense_bwd': [vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, vp],
-    'gn_act_fwd': [vp, vp, sz, i32, f32, vp],
-    'gn_act_bwd': [vp, vp, vp, sz, i32, f32, vp],
-    'gn_act_dropout_bwd': [vp, vp, vp, vp, sz, i32, f32, f32, vp],
-    'gn_set_conv_math': [i32, vp, sz],
-    'gn_conv_fold_bn': [vp, vp, vp, vp, vp, vp, sz, i32, vp],
-    'gn_bn_apply_dropgen': [vp, vp, vp, vp, vp, sz, i32, i32, f32, f32, u64, u64, vp],
-    'gn_bias_act_dropout': [vp, vp, vp, sz, i32, i32, f32, f32, i32, u64, u64, vp],
-    'gn_bias_grad': [vp, vp, vp, sz, sz, i32, vp],
-    'gn_prelu_fwd': [vp, vp, vp, i32, sz, vp],
-    'gn_prelu_bwd': [vp, vp, vp, vp, vp, i32, sz, vp],
-    'gn_dropout_mask': [vp, sz, f32, u64, u64, vp],
-    'gn_dropout_apply': [vp, vp, vp, sz, f32, vp],
-    'gn_upsample2_fwd': [vp, vp, i32, i32, i32, vp],
-    'gn_upsample2_bwd': [vp, vp, i32, i32, i32, vp],
-    'gn_maxpool_h2_fwd': [vp, vp, i32, i32, i32, vp],
-    'gn_maxpool_h2_bwd': [vp, vp, vp, i32, i32, i32, vp],
-    'gn_subtract_stack_fwd': [vp, vp, vp, i32, i32, vp],
-    'gn_subtract_stack_bwd': [vp, vp, i32, i32, vp],
-    'gn_affine_stack_fwd': [vp, vp, vp, f32, f32, vp, i32, i32, vp],
-    'gn_affine_stack_bwd': [vp, f32, f32, vp, i32, i32, vp],
-    'gn_assemble_d_batch': [vp, vp, vp, vp, vp, i32, i32, vp],
-    'gn_fill_uniform': [vp, sz, f32, f32, u64, u64, vp],
-    'gn_fill_normal': [vp, sz, f32, f32, u64, u64, vp],
-    'gn_gather_rows': [vp, vp, vp, i32, i32, vp],
-    'gn_axpy': [vp, vp, f32, sz, vp],
-    'gn_bn_stats': [vp, sz, i32, vp, vp, sz, vp],
-    'gn_bn_finalize': [vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, i32, vp],
-    'gn_bn_finalize_zero_debias': [vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp],
-    'gn_bn_infer_coeffs': [vp, vp, vp, vp, f32, vp, vp, i32, vp],
-    'gn_bn_apply': [vp, vp, vp, vp, vp, sz, i32, i32, f32, f32, vp],
-    'gn_bn_bwd_stats': [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, f32, f32, vp, vp, vp],
-    'gn_bn_bwd_apply': [vp, vp, vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, vp, sz, i32, i32, f32, f32, vp, vp, vp],
-    'gn_bn_bwd_stats_conv1': [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, sz, i32, i32, f32, f32, vp, vp, vp],
-    'gn_bn_bwd_apply_conv1': [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, vp, sz, i32, i32, f32, f32, vp, vp, vp],
-    'gn_bce_loss': [vp, vp, vp, vp, i32, i32, vp],
-    'gn_mse_loss': [vp, vp, vp, vp, i32, i32, vp],
-    'gn_loss_pass': [i32, vp, vp, vp, vp, i64, i32, f64, vp, sz, vp],
-    'gn_weight_count': [vp, i64, vp, vp, sz, vp],
-    'gn_loss_pass_weighted': [i32, vp, vp, vp, vp, vp, vp, i64, i32, vp, sz, vp],
-    'gn_adam_step': [vp, vp, vp, vp, sz, f32, f32, f32, f32, vp],
-    'gn_set_rng_base': [vp],
-    'gn_adam_step_dyn': [vp, vp, vp, vp, sz, vp, f32, f32, f32, vp],
-    'gn_optim_step': [i32, vp, vp, vp, vp, vp, sz, f32, vp, f32, f32, f32, i32, vp, f32, vp],
-    'gn_optim_sumsq': [vp, sz, vp, vp],
-    'gn_optim_clip_factor': [vp, sz, f32, vp, vp],
-    'gn_fill_normal_dyn': [vp, sz, f32, vp, u64, u64, vp],
-    'gn_gaussian_noise_fwd': [vp, vp, sz, f32, u64, u64, vp],
-    'gn_gaussian_dropout_apply': [vp, vp, sz, f32, u64, u64, vp],
-    'gn_alpha_dropout_fwd': [vp, vp, sz, f32, f32, f32, f32, u64, u64, vp],
-    'gn_alpha_dropout_bwd': [vp, vp, sz, f32, f32, u64, u64, vp],
-    'gn_bn_finalize_zero_debias_dyn': [vp, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
-    'gn_prof_enable': [i32],
-    'gn_prof_reset': [],
-    'gn_prof_collect': [i32, vp],
-    'gn_chirp_fd_whitened': [vp, vp, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, vp],
-    'gn_irfft_f64': [vp, vp, vp, i32, i32, vp],
-    'gn_rfft_f64': [vp, vp, vp, i32, i32, vp],
-    'gn_mul_f64': [vp, vp, sz, sz, i32, vp],
-    'gn_align_crop': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, vp],
-    'gn_noise_fd': [vp, vp, i32, i32, u64, u64, vp],
-    'gn_synth_templates': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, f64, f64, vp],
-    'gn_synth_templates_prior': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, f64, f64, u64, u64, i32, i32,
-                                 f64, f64, vp],
-    'gn_noise_whitened': [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, u64, u64, vp],
-    'gn_synth_templates_noise': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, f64, f64,
-                                 u64, u64, i32, i32, f64, f64, u64, u64, vp, vp],
-    'gn_kde2d_pdf': [vp, i32, vp, i32, f64, f64, f64, f64, vp, vp],
-    'gn_scale_f64': [vp, f64, sz, vp],
-    'gn_f64_to_f32': [vp, vp, f64, sz, vp],
-}
-_SIZE_FNS = {
-    'gn_conv1d_bf16x3_workspace': [i32, i32, i32, i32, i32],
-    'gn_conv1d_wino_workspace': [i32, i32],
-    'gn_conv1d_wgrad_workspace': [i32, i32, i32, i32, i32, i32, i32],
-    'gn_dense_bwd_workspace': [i32, i32, i32],
-    'gn_bn_stats_workspace': [sz, i32],
-    'gn_bias_grad_workspace': [sz, i32],
-    'gn_conv1d_fwd_stats_workspace': [i32, i32, i32],
-    'gn_optim_sumsq_slots': [sz],
-    'gn_loss_pass_workspace': [i64, i32],
-    'gn_weight_count_workspace': [i64],
-    'gn_loss_pass_weighted_workspace': [i64, i32],
-}
-
-
-_PREDICATES = {                       # int-valued queries (0 / 1), no error code
-    'gn_conv1d_needs_any': [i32, i32],
-}
+_ARG_TYPES = {'int': i32, 'float': f32, 'double': f64, 'size_t': sz, 'uint64_t': u64, 'long long': i64, '*': vp}      # '*': any pointer
+_RETURN_TYPES = {'int': i32, 'size_t': sz, 'const char*': C.c_char_p}
 
 
 class GennetHipError(RuntimeError):
     pass
+
+
+def read_header(text):
+    """({name: (restype, [argtypes])}, {constant: int}) of the text of gennet_hip.h: its `gn_*` declarations as ctypes, its integer
+    #defines and its enum members.  A reader for the vocabulary of that header, not a C parser: a type it does not know, or a statement it
+    cannot split, raises GennetHipError naming the declaration."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    consts = dict((k, int(v)) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(GN_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, re.M))
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+    text = re.sub(r'\}\s*$', '', re.sub(r'extern\s+"C"\s*\{', ' ', text))           # the extern "C" { } around the declarations
+    fns = {}
+    *statements, rest = text.split(';')
+    if rest.strip():
+        raise GennetHipError('gennet_hip.h: no ; after %r' % ' '.join(rest.split()))
+    for s in statements:
+        s = ' '.join(s.split())
+        enum = re.fullmatch(r'enum \w+ ?\{([^{}]*)\}', s)
+        if enum:
+            for member in enum.group(1).split(','):
+                m = re.fullmatch(r'\s*(GN_\w+) = (-?\d+)\s*', member)
+                if not m:
+                    raise GennetHipError('gennet_hip.h: enum member %r of %r has no integer value' % (member.strip(), s))
+                consts[m.group(1)] = int(m.group(2))
+            continue
+        decl = re.fullmatch(r'([^()]+?) ?\b(gn_\w+) ?\(([^()]*)\)', s)
+        if not decl:
+            raise GennetHipError('gennet_hip.h: cannot read the declaration %r' % s)
+        ret, name, params = decl.groups()
+        ret = re.sub(r' ?\* ?', '*', ret)
+        args = []
+        for p in ([] if params.strip() in ('', 'void') else params.split(',')):
+            base = '*' if '*' in p else ' '.join(w for w in p.split()[:-1] if w != 'const')      # the last word is the parameter's name
+            if base not in _ARG_TYPES:
+                raise GennetHipError('gennet_hip.h: unknown parameter type %r in %r' % (p.strip(), s))
+            args.append(_ARG_TYPES[base])
+        if ret not in _RETURN_TYPES:
+            raise GennetHipError('gennet_hip.h: unknown return type %r in %r' % (ret, s))
+        fns[name] = (_RETURN_TYPES[ret], args)
+    return fns, consts
+
+
+with open(build.HEADER) as _f:
+    DECLS, CONSTS = read_header(_f.read())
+GN_OK, GN_EINVAL, GN_ELAUNCH, GN_EWORKSPACE = (CONSTS[_k] for _k in ('GN_OK', 'GN_EINVAL', 'GN_ELAUNCH', 'GN_EWORKSPACE'))
+
+
+def enum_members(prefix):
+    """{lower-cased suffix: value} of the header's constants that start with `prefix`, in the header's order."""
+    return dict((k[len(prefix):].lower(), v) for k, v in CONSTS.items() if k.startswith(prefix))
 
 
 def lib():
@@ -138,8 +79,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             try:                            # a fresh checkout on a box that has hipcc: compile the kernels (~30 s), nothing else
-                from . import build as _build
-                _build.build(verbose=False)
+                build.build(verbose=False)
             except Exception as e:          # noqa: BLE001
                 raise GennetHipError('%s not found and building it failed (%s): run `python -m gennet_amd.build` '
                                      '(hipcc --offload-arch=gfx950); gennet_amd has no CPU fallback' % (LIB_PATH, e))
@@ -148,43 +88,40 @@ def lib():
         # already-loaded copy.  Loading in the other order gives the process two HIP runtimes and launches fail.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table, restype in ((_SIGS, i32), (_SIZE_FNS, sz), (_PREDICATES, i32)):
-            for name, args in table.items():
-                try:
-                    fn = getattr(L, name)
-                except AttributeError:      # reported by call()/size() and by tests/test_capi_symbols.py
-                    continue
-                fn.argtypes = args
-                fn.restype = restype
-        L.gn_last_error.restype = C.c_char_p
-        L.gn_version.restype = i32
+        for name, (restype, argtypes) in DECLS.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:          # reported by call() / size() / predicate() and by tests/test_host_cpu.py
+                continue
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = L
     return _lib
 
 
 def exported_symbols():
-    return sorted(list(_SIGS) + list(_SIZE_FNS) + list(_PREDICATES) + ['gn_last_error', 'gn_version'])
+    return sorted(DECLS)
+
+
+def _fn(name, restype):
+    """The bound function `name`, which the header must declare as returning `restype`."""
+    if DECLS.get(name, (None,))[0] is not restype:
+        raise GennetHipError('%s is not declared in %s as returning %s' % (name, os.path.basename(build.HEADER), restype.__name__))
+    try:
+        return getattr(lib(), name)
+    except AttributeError:
+        raise GennetHipError('%s is not exported by %s (stale build?)' % (name, LIB_PATH))
 
 
 def call(name, *args):
-    L = lib()
-    try:
-        fn = getattr(L, name)
-    except AttributeError:
-        raise GennetHipError('%s is not exported by %s (stale build?)' % (name, LIB_PATH))
-    rc = fn(*args)
+    rc = _fn(name, i32)(*args)
     if rc != 0:
-        raise GennetHipError('%s failed (%d): %s' % (name, rc, L.gn_last_error().decode()))
+        raise GennetHipError('%s failed (%d): %s' % (name, rc, lib().gn_last_error().decode()))
 
 
 def size(name, *args):
-    return int(getattr(lib(), name)(*args))
+    return int(_fn(name, sz)(*args))
 
 
 def predicate(name, *args):
-    L = lib()
-    try:
-        fn = getattr(L, name)
-    except AttributeError:
-        raise GennetHipError('%s is not exported by %s (stale build?)' % (name, LIB_PATH))
-    return bool(fn(*args))
+    return bool(_fn(name, i32)(*args))

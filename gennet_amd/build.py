@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libgennet_hip.so')
+HEADER = os.path.join(HERE, '..', 'include', 'gennet_hip.h')      # the one declaration of the C ABI: compiled against here, read by _lib.py
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-ffp-contract=off', '-Wall', '-Wno-unused-function']
 # development only (timing-ablation builds, -DGN_ABLATION: kernels that skip work and return wrong results); never set for the shipped library
@@ -36,7 +37,7 @@ def build(force=False, verbose=True):
     objdir = os.path.join(LIBDIR, 'obj')
     os.makedirs(objdir, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip')))
-    hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(HERE, '..', 'include', 'gennet_hip.h')]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [HEADER]
     jobs = []
     objs = []
     for s in srcs:

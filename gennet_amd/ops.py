@@ -3,11 +3,15 @@
 Every function takes / returns contiguous fp32 CUDA tensors in Keras channels-last layout and launches on
 torch's current stream.  No function here computes anything itself.
 """
+import ctypes
+import functools
+
 import torch
 
 from . import _lib
 
-ACT = {'linear': 0, None: 0, 'relu': 1, 'relu_max': 2, 'leaky': 3, 'tanh': 4, 'sigmoid': 5}
+ACT = _lib.enum_members('GN_ACT_')                              # enum gn_act ...
+ACT[None] = ACT['linear']                                       # ... and Keras' activation=None
 
 _ws = {}
 
@@ -260,10 +264,13 @@ def maxpool_h2_bwd(dy, x):
     return dx
 
 
+@functools.lru_cache(maxsize=None)
 def tap_groups(k):
-    """(G, h): a k-tap Conv1D (k > 5) runs as G = ceil(k/5) tap groups of h = ceil(k/G) taps (gn_conv1d_tap_groups, csrc/tap_fold.hip)."""
-    G = (k + 4) // 5
-    return G, (k + G - 1) // G
+    """(G, h): a k-tap Conv1D (k > 5) runs as G = ceil(k/5) tap groups of h = ceil(k/G) taps; gn_conv1d_tap_groups (csrc/tap_fold.hip) owns the
+    rule, asked once per k (a host-only call: nothing is launched)."""
+    G, h = ctypes.c_int(), ctypes.c_int()
+    _lib.call('gn_conv1d_tap_groups', k, ctypes.byref(G), ctypes.byref(h))
+    return G.value, h.value
 
 
 def conv1d_tapfold_x(x, k, pl):
@@ -728,9 +735,8 @@ def loss(kind, p, y, Bglobal=None):
     return dp, out
 
 
-LOSS_KINDS = {'binary_crossentropy': 0, 'mean_squared_error': 1, 'mean_absolute_error': 2, 'mean_absolute_percentage_error': 3,
-              'mean_squared_logarithmic_error': 4, 'hinge': 5, 'squared_hinge': 6, 'logcosh': 7, 'poisson': 8, 'kullback_leibler_divergence': 9,
-              'categorical_crossentropy': 10, 'cosine_proximity': 11, 'categorical_accuracy': 12}       # enum gn_loss
+LOSS_KINDS = _lib.enum_members('GN_LOSS_')                      # enum gn_loss ...
+del LOSS_KINDS['kinds']                                         # ... without its count, GN_LOSS_KINDS
 LOSS_ALIASES = {'mse': 'mean_squared_error', 'mae': 'mean_absolute_error', 'mape': 'mean_absolute_percentage_error',
                 'msle': 'mean_squared_logarithmic_error', 'kld': 'kullback_leibler_divergence', 'cosine': 'cosine_proximity'}
 # element count from which the engine sends binary_crossentropy / mean_squared_error to loss_pass instead of the one-block kernel of loss():
@@ -793,7 +799,7 @@ def adam_step(p, g, m, v, lr_t, b1, b2, eps):
         _lib.call('gn_adam_step', _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr_t), float(b1), float(b2), float(eps), _stream())
 
 
-OPT_RULES = {'sgd': 0, 'rmsprop': 1, 'adagrad': 2, 'adadelta': 3, 'adamax': 4, 'adam': 5, 'amsgrad': 6}
+OPT_RULES = _lib.enum_members('GN_OPT_')                        # enum gn_optim_rule
 
 
 def optim_step(rule, p, g, states, lr, h0=0.0, h1=0.0, eps=0.0, nesterov=False, clip_scale=None, clipvalue=0.0):

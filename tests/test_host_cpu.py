@@ -14,16 +14,36 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = np.load(os.path.join(ROOT, 'tests', 'golden', 'synth_golden.npz'))
 
 
+def _defined_dynamic_symbols(so):
+    """Names of the defined dynamic symbols of a shared library: llvm-readelf of the ROCm installation that holds build.HIPCC, else nm -D."""
+    import shutil
+    import subprocess
+    from gennet_amd import build
+    hipcc = shutil.which(build.HIPCC) or build.HIPCC
+    readelf = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), 'llvm', 'bin', 'llvm-readelf')
+    if os.path.exists(readelf):
+        rows = [l.split() for l in subprocess.run([readelf, '--dyn-syms', '--wide', so], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()]
+        return set(r[7].split('@')[0] for r in rows if len(r) == 8 and r[0].rstrip(':').isdigit() and r[6] != 'UND')     # Num Value Size Type Bind Vis Ndx Name
+    nm = shutil.which('nm')
+    assert nm, 'neither %s nor nm exists: the exports of %s cannot be read' % (readelf, so)
+    rows = [l.split() for l in subprocess.run([nm, '-D', '--defined-only', so], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()]
+    return set(r[-1].split('@')[0] for r in rows if len(r) >= 2)
+
+
 def test_library_exports_every_declared_symbol():
+    """The built library defines exactly the gn_* functions that the header declares: none missing, and none exported without a declaration
+    (the binding is derived from the header, so an undeclared export could not be called with checked types)."""
     from gennet_amd import _lib, build
     build.build(verbose=False)
     hdr = open(os.path.join(ROOT, 'include', 'gennet_hip.h')).read()
     declared = set(re.findall(r'\b(gn_[a-z0-9_]+)\s*\(', hdr))
-    assert len(declared) >= 45
+    assert len(declared) >= 105
+    assert declared == set(_lib.exported_symbols()) == set(_lib.DECLS)       # this regex and _lib.read_header agree on the names
     L = ctypes.CDLL(_lib.LIB_PATH)
     missing = [s for s in sorted(declared) if not hasattr(L, s)]
     assert not missing, missing
-    assert declared == set(_lib.exported_symbols()), declared ^ set(_lib.exported_symbols())
+    defined = set(s for s in _defined_dynamic_symbols(_lib.LIB_PATH) if s.startswith('gn_'))
+    assert defined == declared, (sorted(defined - declared), sorted(declared - defined))
     L.gn_version.restype = ctypes.c_int
     assert L.gn_version() >= 100
 
@@ -58,7 +78,7 @@ def test_conv_math_workspace_rules_at_the_c_abi():
 
     shapes = [(64, 128, 1), (1024, 2688, 1), (1024, 2752, 1), (1024, 2304, 2), (1024, 2368, 2)]
     direct = [query(*s) for s in shapes]
-    assert L.gn_set_conv_math(2, fake, ctypes.c_size_t(ops.WINO_WS_BYTES - 1)) == -3            # GN_EWORKSPACE
+    assert L.gn_set_conv_math(2, fake, ctypes.c_size_t(ops.WINO_WS_BYTES - 1)) == _lib.GN_EWORKSPACE
     assert b'workspace' in L.gn_last_error()
     assert [query(*s) for s in shapes] == direct                                                # still math 0
     try:
