@@ -417,6 +417,11 @@ class Layer(object):
     def compute_output_shape(self, input_shape):
         return input_shape
 
+    def get_config(self):
+        """keras' layer config, as model.save writes it (keras_io.layer_config)"""
+        from . import keras_io
+        return keras_io.layer_config(self)
+
     # A subclass that defines keras' `call(self, x)` (and not this engine's forward/backward) is a USER-DEFINED layer in keras'
     # conventions (bbhMahoGANy.py:164-188): its build / compute_output_shape see shapes WITH the batch axis, and its call is traced
     # once on a symbolic operand and lowered to a HIP kernel (gennet_amd/keras/backend.py).
@@ -937,7 +942,10 @@ class Model(Layer):
             if n.absorbed:
                 continue
             tail = n
-            if n.layer.fusable_act:
+            # a layer with a non-linear activation of its own (Dense, Conv1D, Conv2D, Conv2DTranspose(activation=...)) has its epilogue taken: an
+            # activation layer behind it runs as its own pass, act2(act1(z)) as keras computes it, and a Dropout behind that one follows it
+            own_act = getattr(n.layer, 'activation', None)
+            if n.layer.fusable_act and (own_act is None or own_act[0] == 'linear'):
                 c = sole_consumer(tail.index)
                 if c is not None and c.layer.act_spec is not None:
                     n.fused_act = c.layer.act_spec

@@ -192,7 +192,7 @@ def layer_config(layer):
         cfg.update(filters=layer.filters, kernel_size=[layer.kh, layer.kw], strides=[layer.sh, layer.sw], padding=layer.padding,
                    data_format='channels_last', dilation_rate=[1, 1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
     elif isinstance(layer, L.BatchNormalization):
-        cfg.update(axis=-1, momentum=layer.momentum, epsilon=layer.epsilon, center=True, scale=True, beta_initializer=_ZEROS, gamma_initializer=_ONES,
+        cfg.update(axis=layer.axis, momentum=layer.momentum, epsilon=layer.epsilon, center=True, scale=True, beta_initializer=_ZEROS, gamma_initializer=_ONES,
                    moving_mean_initializer=_ZEROS, moving_variance_initializer=_ONES, beta_regularizer=None, gamma_regularizer=None,
                    beta_constraint=None, gamma_constraint=None)
     elif isinstance(layer, L.PReLU):
@@ -375,7 +375,8 @@ STATE_GROUP = 'gennet_amd_state'      # private root group (not a keras layer gr
 
 
 def _bn_layers(model):
-    return [l for l in model.layers if getattr(l, 'is_batchnorm', False)]
+    from .layers import BatchNormalization
+    return [l for l in model.layers if isinstance(l, BatchNormalization)]        # over any axis (is_batchnorm: the channel ones only)
 
 
 def save_private_state(root, model):

@@ -145,14 +145,8 @@ class Dense(Layer):
     def compute_output_shape(self, input_shape):
         return (self.units,)
 
-    def _act(self, node):
-        a = node.fused_act or self.activation
-        if node.fused_act is not None and self.activation[0] != 'linear':
-            raise NotImplementedError('Dense(activation=...) followed by another activation layer')
-        return a
-
     def forward(self, ctx, node, x):
-        a = self._act(node)
+        a = node.fused_act or self.activation
         y = ops.dense_fwd(x, self.kernel.data, self.bias.data, a[0], a[1])
         ctx.tape[node.index] = (x, y, a)
         if ctx.training and a[0] != 'linear':
@@ -407,13 +401,8 @@ class Conv2DTranspose(Layer):
     def compute_output_shape(self, input_shape):
         return (input_shape[0], self.out_length(input_shape[1]), self.filters)
 
-    def _act(self, node):
-        if node.fused_act is not None and self.activation[0] != 'linear':
-            raise NotImplementedError('Conv2DTranspose(activation=...) followed by another activation layer')
-        return node.fused_act or self.activation
-
     def forward(self, ctx, node, x):
-        a = self._act(node)
+        a = node.fused_act or self.activation
         B, H, W, Cin = x.shape
         Wout = self.out_length(W)
         pl = ops.conv_geometry(Wout, self.k, self.stride, self.padding)[1]
@@ -457,6 +446,12 @@ class BatchNormalization(Layer):
     A following Activation and Dropout run in the same pass (one read, one write).  Under data parallelism the
     statistics are all-reduced (SyncBN) so that N ranks x B/N rows reproduce a single-device batch of B.
 
+    axis: keras' axis, counting the batch dimension (1..n-1 or -1..-(n-1) for rank-n inputs).  The last axis (-1 or n-1) is the channel
+    BatchNormalization described above.  Any other axis -- BatchNormalization(axis=1) on (B, L, C) in the reference's 2_model_version models: one
+    gamma / beta / moving pair per position l, statistics over the batch and the channels -- runs the plain passes of csrc/bn_axis.hip over
+    the (outer, P, inner) view with the same finalize, moving-average forms and all-reduce, fuses with nothing, and is no BatchNormalization
+    for the planner (is_batchnorm, fusable_act, fusable_drop are per instance).
+
     moving_average = 'tf_zero_debias' (default) reproduces keras 2.2.4 on its TF 1.12 backend: K.moving_average_update calls
     tf moving_averages.assign_moving_average(x, value, momentum, zero_debias=True), which keeps a zero-initialised `biased` shadow
     accumulator and a `local_step` counter and sets moving = biased / (1 - momentum^local_step): the moving statistics forget their
@@ -466,13 +461,12 @@ class BatchNormalization(Layer):
     (layer, training model).  The pairs are not keras weights: real keras never writes them to .h5 files and starts them from zero
     after load_weights; keras_io keeps them in a private section of files written here.
     moving_average = 'ema': the plain exponential average (zero_debias=False; what tf.keras and later keras versions do)."""
-    fusable_act = True
-    fusable_drop = True
-
     def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, moving_average=None, **kw):
         Layer.__init__(self, **kw)
-        if axis != -1:
-            raise NotImplementedError('BatchNormalization(axis=%r)' % (axis,))
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+            raise NotImplementedError('BatchNormalization(axis=%r): one integer axis' % (axis,))
+        self.axis = int(axis)              # keras' axis, counting the batch dimension; written back as given (keras_io)
+        self.view = None                   # build: (rows of `outer` per sample, P, inner) of the (outer, P, inner) view, P = the normalised axis
         self.momentum, self.epsilon = float(momentum), float(epsilon)
         self.moving_average = moving_average or BN_MOVING_AVERAGE
         if self.moving_average not in ('tf_zero_debias', 'ema'):
@@ -488,27 +482,31 @@ class BatchNormalization(Layer):
         return st
 
     def build(self, input_shape):
-        C = input_shape[-1]
+        n = len(input_shape) + 1           # rank with the batch dimension
+        if not (1 <= self.axis <= n - 1 or -(n - 1) <= self.axis <= -1):
+            raise ValueError('BatchNormalization(axis=%d) on inputs of shape %r: the axis must be one of 1..%d or -1..-%d'
+                             % (self.axis, (None,) + tuple(input_shape), n - 1, n - 1))
+        k = (self.axis if self.axis > 0 else self.axis + n) - 1
+        C = int(input_shape[k])
+        self.view = (int(np.prod(input_shape[:k], dtype=np.int64)), C, int(np.prod(input_shape[k + 1:], dtype=np.int64)))
+        self._last_axis = k == len(input_shape) - 1
         self.gamma = self.add_weight('gamma', np.ones(C, np.float32))
         self.beta = self.add_weight('beta', np.zeros(C, np.float32))
         self.moving_mean = self.add_weight('moving_mean', np.zeros(C, np.float32), trainable=False)
         self.moving_variance = self.add_weight('moving_variance', np.ones(C, np.float32), trainable=False)
 
-    is_batchnorm = True
+    @property
+    def is_batchnorm(self):
+        """A channel (last-axis) BatchNormalization: what the planner and the conv layers fuse with -- activation and Dropout in the apply pass,
+        the fold into the producing conv in predict, ctx.bn_sums from its epilogue, the deferred data gradient (lazy_bn).  Over any other axis
+        the layer takes part in none of that and runs its plain passes.  (Before build only -1 is known to be the last axis.)"""
+        return self._last_axis if self.view is not None else self.axis == -1
 
-    def forward(self, ctx, node, x):
-        if node.index in ctx.skip:         # inference phase: already folded into the producing convolution
-            return x
-        C = x.shape[-1]
-        x2 = x.reshape(-1, C)
-        act = node.fused_act or ('linear', 0.0)
-        if not ctx.training:
-            scale, shift = ops.bn_infer_coeffs(self.gamma.data, self.beta.data, self.moving_mean.data, self.moving_variance.data, self.epsilon)
-            return ops.bn_apply(x2, scale, shift, None, act[0], act[1]).reshape(x.shape)
-        sums = ctx.bn_sums.pop(node.index, None)          # handed over by the producing convolution's epilogue, if it had one
-        if sums is None:
-            sums = ops.bn_stats(x2)
-        count = x2.shape[0]
+    fusable_act = fusable_drop = is_batchnorm
+
+    def _train_coeffs(self, ctx, sums, count):
+        """all-reduce of the statistics, finalize and moving-statistics update of the training phase -> (scale, shift, save_mean, save_invstd, count),
+        count the number of elements reduced per parameter over all ranks"""
         if ctx.dp is not None:
             ctx.dp.all_reduce_sum(sums)
             count *= ctx.dp.world_size
@@ -525,8 +523,29 @@ class BatchNormalization(Layer):
                     st[2] += 1
                     return st[2]
                 zd = (st[0], st[1], cap.slot('i', next_step))
-        scale, shift, smean, sinv = ops.bn_finalize(sums, count, self.gamma.data, self.beta.data, self.epsilon, self.momentum,
-                                                    self.moving_mean.data, self.moving_variance.data, zd)
+        return ops.bn_finalize(sums, count, self.gamma.data, self.beta.data, self.epsilon, self.momentum,
+                               self.moving_mean.data, self.moving_variance.data, zd) + (count,)
+
+    def _param_grads(self, need_dw):
+        if need_dw:
+            return self.gamma.grad, self.beta.grad
+        return torch.empty_like(self.gamma.data), torch.empty_like(self.beta.data)
+
+    def forward(self, ctx, node, x):
+        if not self.is_batchnorm:
+            return self._forward_axis(ctx, node, x)
+        if node.index in ctx.skip:         # inference phase: already folded into the producing convolution
+            return x
+        C = x.shape[-1]
+        x2 = x.reshape(-1, C)
+        act = node.fused_act or ('linear', 0.0)
+        if not ctx.training:
+            scale, shift = ops.bn_infer_coeffs(self.gamma.data, self.beta.data, self.moving_mean.data, self.moving_variance.data, self.epsilon)
+            return ops.bn_apply(x2, scale, shift, None, act[0], act[1]).reshape(x.shape)
+        sums = ctx.bn_sums.pop(node.index, None)          # handed over by the producing convolution's epilogue, if it had one
+        if sums is None:
+            sums = ops.bn_stats(x2)
+        scale, shift, smean, sinv, count = self._train_coeffs(ctx, sums, x2.shape[0])
         mask, rate = None, 0.0
         if node.fused_drop is not None and node.fused_drop[0] > 0.0:
             rate, drop_layer = node.fused_drop
@@ -550,6 +569,8 @@ class BatchNormalization(Layer):
         return y.reshape(x.shape)
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
+        if not self.is_batchnorm:
+            return self._backward_axis(ctx, node, dy, need_dw)
         x2, mask, smean, sinv, count, act, rate, scale, shift = ctx.tape.pop(node.index)
         y = None                       # any channel count: the activation output is recomputed from x2 with scale / shift
         lazy = isinstance(dy, ops.ConvGrad1)
@@ -562,14 +583,44 @@ class BatchNormalization(Layer):
         if ctx.dp is not None:
             glob = local.clone()
             ctx.dp.all_reduce_sum(glob)
-        if need_dw:
-            dgamma, dbeta = self.gamma.grad, self.beta.grad
-        else:
-            dgamma = torch.empty_like(self.gamma.data); dbeta = torch.empty_like(self.beta.data)
+        dgamma, dbeta = self._param_grads(need_dw)
         if lazy:
             dx = ops.bn_bwd_apply_conv1(dy, x2, mask, self.gamma.data, smean, sinv, glob, count, local, dgamma, dbeta, act[0], act[1], rate, scale, shift)
         else:
             dx = ops.bn_bwd_apply(dy2, y, x2, mask, self.gamma.data, smean, sinv, glob, count, local, dgamma, dbeta, act[0], act[1], rate, scale, shift)
+        return dx.reshape(dy.shape)
+
+    # -- any axis but the last: the plain sequence statistics -> all-reduce -> finalize -> apply over the (outer, P, inner) view, nothing fused.
+    # inner >= 2 runs csrc/bn_axis.hip; inner == 1 is a last-axis layout and runs the column kernels on its (outer, P) view.  By shape alone.
+    def _forward_axis(self, ctx, node, x):
+        P, inner = self.view[1], self.view[2]
+        xv = x.contiguous().reshape((-1, P) if inner == 1 else (-1, P, inner))
+        apply_ = ops.bn_apply if inner == 1 else ops.bn_axis_apply
+        if not ctx.training:
+            scale, shift = ops.bn_infer_coeffs(self.gamma.data, self.beta.data, self.moving_mean.data, self.moving_variance.data, self.epsilon)
+            return apply_(xv, scale, shift).reshape(x.shape)
+        sums = ops.bn_stats(xv) if inner == 1 else ops.bn_axis_stats(xv)
+        scale, shift, smean, sinv, count = self._train_coeffs(ctx, sums, xv.shape[0] * inner)
+        # scale / shift: 2 P floats, asked for by the column kernels' backward in place of the layer output (which no pass reads: no activation)
+        ctx.tape[node.index] = (xv, smean, sinv, count, scale, shift)
+        return apply_(xv, scale, shift).reshape(x.shape)
+
+    def _backward_axis(self, ctx, node, dy, need_dw):
+        xv, smean, sinv, count, scale, shift = ctx.tape.pop(node.index)
+        dyv = dy.contiguous().reshape(xv.shape)
+        if xv.dim() == 2:
+            local = ops.bn_bwd_stats(dyv, None, xv, None, smean, sinv, scale=scale, shift=shift)
+        else:
+            local = ops.bn_axis_bwd_stats(dyv, xv, smean, sinv)
+        glob = local
+        if ctx.dp is not None:
+            glob = local.clone()
+            ctx.dp.all_reduce_sum(glob)
+        dgamma, dbeta = self._param_grads(need_dw)
+        if xv.dim() == 2:
+            dx = ops.bn_bwd_apply(dyv, None, xv, None, self.gamma.data, smean, sinv, glob, count, local, dgamma, dbeta, scale=scale, shift=shift)
+        else:
+            dx = ops.bn_axis_bwd_apply(dyv, xv, self.gamma.data, smean, sinv, glob, count, local, dgamma, dbeta)
         return dx.reshape(dy.shape)
 
 

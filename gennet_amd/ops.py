@@ -691,6 +691,51 @@ def bn_bwd_apply(dy2d, y2d, x2d, mask, gamma, smean, sinv, dsums_global, count, 
     return dx
 
 
+# the same four passes over an axis that is not the last one: x3d an (outer, P, inner) view, one parameter per p (csrc/bn_axis.hip); no
+# activation, no mask.  bn_finalize / bn_infer_coeffs serve them with P parameters and count = outer * inner.
+def _axis_ws(x3d):
+    outer, P, inner = x3d.shape
+    return workspace(_lib.size('gn_bn_axis_stats_workspace', outer, P, inner), x3d.device)
+
+
+def bn_axis_stats(x3d):
+    """-> fp64 sums (2*P,): [sum over (o, i) of x | of x^2]."""
+    _chk(x3d)
+    outer, P, inner = x3d.shape
+    sums = torch.empty((2 * P,), dtype=torch.float64, device=x3d.device)
+    ws = _axis_ws(x3d)
+    _lib.call('gn_bn_axis_stats', _p(x3d), outer, P, inner, _p(sums), _p(ws), ws.numel(), _stream())
+    return sums
+
+
+def bn_axis_apply(x3d, scale, shift):
+    _chk(x3d)
+    outer, P, inner = x3d.shape
+    y = torch.empty_like(x3d)
+    _lib.call('gn_bn_axis_apply', _p(x3d), _p(scale), _p(shift), _p(y), outer, P, inner, _stream())
+    return y
+
+
+def bn_axis_bwd_stats(dy3d, x3d, smean, sinv):
+    """-> fp64 dsums (2*P,): [sum dy | sum dy * xhat]."""
+    _chk(dy3d, x3d)
+    outer, P, inner = x3d.shape
+    dsums = torch.empty((2 * P,), dtype=torch.float64, device=x3d.device)
+    ws = _axis_ws(x3d)
+    _lib.call('gn_bn_axis_bwd_stats', _p(dy3d), _p(x3d), _p(smean), _p(sinv), _p(dsums), _p(ws), ws.numel(), outer, P, inner, _stream())
+    return dsums
+
+
+def bn_axis_bwd_apply(dy3d, x3d, gamma, smean, sinv, dsums_global, count, dsums_local, dgamma, dbeta):
+    _chk(dy3d, x3d)
+    outer, P, inner = x3d.shape
+    dx = torch.empty_like(x3d)
+    ws = _axis_ws(x3d)
+    _lib.call('gn_bn_axis_bwd_apply', _p(dy3d), _p(x3d), _p(gamma), _p(smean), _p(sinv), _p(dsums_global), float(count), _p(dsums_local), _p(dx),
+              _p(dgamma), _p(dbeta), _p(ws), ws.numel(), outer, P, inner, _stream())
+    return dx
+
+
 class ConvGrad1(object):
     """The data gradient of a Conv1D(1 filter, k taps, stride 1), NOT materialised: g (B, Lout, 1) the conv's output gradient, w (k, C, 1)
     its kernel, L the conv's input length.  Consumed by bn_bwd_stats_conv1 / bn_bwd_apply_conv1 (gn_bn_bwd_*_conv1)."""

@@ -297,6 +297,31 @@ int gn_bn_bwd_apply_conv1(const float* g, const float* w, int L, int Lout, int k
                           const double* dsums_local, float* dx, float* dgamma, float* dbeta, size_t rows, int C, int act, float act_param,
                           float rate, const float* scale, const float* shift, void* stream);
 
+/* ---- BatchNormalization over an axis that is not the last one (csrc/bn_axis.hip): keras BatchNormalization(axis=1) on (B, L, C), one
+ * gamma / beta / moving_mean / moving_variance per position l, statistics over the batch and the channels ----
+ * x is viewed as (outer, P, inner): element (o, p, i) at (o*P + p)*inner + i; P the normalised axis, outer the product of the dimensions
+ * in front of it (the batch included), inner the product of those behind it.  Any outer, P, inner >= 1 with P*inner < 2^31; inner % 4 == 0
+ * on 16-byte aligned tensors runs with 16-byte loads and stores, anything else with scalar ones.  inner == 1 is the last-axis case
+ * (rows = outer, C = P) that gn_bn_stats ... gn_bn_bwd_apply serve; it is accepted here and computes the same.
+ * No activation, no dropout mask.  gn_bn_finalize(_zero_debias(_dyn)) and gn_bn_infer_coeffs run between the passes with C := P and
+ * count = outer*inner (times the world size after the all-reduce of sums / dsums).
+ * Bytes per element: stats reads 4; apply reads 4, writes 4; bwd_stats reads 8; bwd_apply reads 8, writes 4.
+ * Both reductions sum in a fixed order (per-block fp64 partials in ws, then summed chunk by chunk): repeated runs give identical bits.
+ * ws: gn_bn_axis_stats_workspace(outer, P, inner) bytes serve all three calls that take one. */
+size_t gn_bn_axis_stats_workspace(size_t outer, int P, int inner);
+/* sums[0:P] = sum over (o, i) of x, sums[P:2P] = sum of x^2 (fp64) */
+int gn_bn_axis_stats(const float* x, size_t outer, int P, int inner, double* sums, void* ws, size_t ws_bytes, void* stream);
+/* y = fma(x, scale[p], shift[p]): gn_bn_apply's expression; both phases */
+int gn_bn_axis_apply(const float* x, const float* scale, const float* shift, float* y, size_t outer, int P, int inner, void* stream);
+/* dsums[0:P] = sum dy, dsums[P:2P] = sum dy*xhat, xhat = (x - save_mean[p])*save_invstd[p] (fp64) */
+int gn_bn_axis_bwd_stats(const float* dy, const float* x, const float* save_mean, const float* save_invstd, double* dsums, void* ws,
+                         size_t ws_bytes, size_t outer, int P, int inner, void* stream);
+/* dx = gamma[p]*invstd[p]*(dy - dsum[p]/n - xhat*dsum_xhat[p]/n) from dsums_global and count = n; dbeta = dsums_local[0:P],
+ * dgamma = dsums_local[P:2P] as fp32.  ws (>= 12*P bytes) holds the three per-position constants, formed once in front of the pass. */
+int gn_bn_axis_bwd_apply(const float* dy, const float* x, const float* gamma, const float* save_mean, const float* save_invstd,
+                         const double* dsums_global, double count, const double* dsums_local, float* dx, float* dgamma, float* dbeta,
+                         void* ws, size_t ws_bytes, size_t outer, int P, int inner, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
