@@ -2,7 +2,7 @@
 //
 // The tensor is viewed as (outer, P, inner): element (o, p, i) lives at (o*P + p)*inner + i, P the normalised axis, outer everything in
 // front of it (the batch included), inner everything behind it.  A parameter p owns `outer` contiguous runs of `inner` floats, P*inner
-// floats apart -- not the columns that colred_kernel (elementwise.hip) sums, and a different parameter index in the streaming passes.
+// floats apart -- not the columns that colred_kernel (bn.hip) sums, and a different parameter index in the streaming passes.
 // Four passes, no activation, no dropout mask, nothing fused:
 //   stats      sums  = [sum x | sum x^2]         per p, fp64     4 bytes / element
 //   apply      y     = fma(x, scale[p], shift[p])                 8 bytes / element

@@ -1,6 +1,8 @@
-// extern "C" surface of libgennet_hip.so (see include/gennet_hip.h).  Argument checking, tap-table construction, the library switches and
-// the kernel-family selection of every convolution (select_conv / select_dgrad / select_wgrad: one table below) live here; no torch types, no
-// allocation, no synchronisation.
+// The library core and the convolutions of libgennet_hip.so.  Core: the error text, the launch check, the profiling events, the library
+// switches and the RNG base of a captured step.  Convolutions: argument checking, tap-table construction and the kernel-family selection of
+// every Conv1D and Dense entry point (select_conv / select_dgrad / select_wgrad: one table below); a Dense layer is the 1-tap conv.  Every
+// other entry point of include/gennet_hip.h is defined beside its kernels, in the file that holds them.  No torch types, no allocation, no
+// synchronisation.
 #include <stdarg.h>
 #include <algorithm>
 #include <mutex>
@@ -234,48 +236,6 @@ static int set_conv_math_impl(int mode, void* workspace, size_t workspace_bytes)
   return GN_OK;
 }
 
-// small C (< 4 or not a multiple of 4) column sums: fp64 block partials + fp64 atomics
-__global__ void colsum_anyc_kernel(const float* __restrict__ x, double* __restrict__ acc, size_t n, int C) {
-  double s[4] = {0, 0, 0, 0};
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int c = (int)(i % C);
-    const double v = (double)x[i];
-    s[0] += c == 0 ? v : 0.0; s[1] += c == 1 ? v : 0.0; s[2] += c == 2 ? v : 0.0; s[3] += c == 3 ? v : 0.0;
-  }
-  __shared__ double red[4][256];
-  for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = s[c];
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft)
-      for (int c = 0; c < 4; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x < C) atomicAdd(&acc[threadIdx.x], red[threadIdx.x][0]);
-}
-__global__ void f64_to_f32_small_kernel(const double* __restrict__ a, float* __restrict__ o, int n) {
-  if ((int)threadIdx.x < n) o[threadIdx.x] = (float)a[threadIdx.x];
-}
-
-// db[c] = sum over rows of dy[row, c]; ws needs colred_workspace_bytes(rows, C) (C % 4 == 0 or C > 4) or 32 bytes otherwise.  C > 4 runs
-// the fixed-order column reduction (colred_run: its any-C kernel when C % 4 != 0), so repeated runs are bit-identical.
-static int bias_grad(const float* dy, float* db, size_t rows, int C, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (C % 4 == 0 || C > 4) {
-    ColRedArgs r = {};
-    r.a = dy; r.rows = rows; r.C = C;
-    return colred_run(0, r, ws, ws_bytes, nullptr, db, s);
-  }
-  if (ws_bytes < 32) { set_error("bias_grad: workspace too small"); return GN_EWORKSPACE; }
-  (void)hipMemsetAsync(ws, 0, 32, s);
-  size_t g = (rows * C + 255) / 256;
-  if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(colsum_anyc_kernel, dim3((unsigned)g), dim3(256), 0, s, dy, (double*)ws, rows * C, C);
-  hipLaunchKernelGGL(f64_to_f32_small_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, db, C);
-  return check_launch("bias_grad");
-}
-
-static size_t bias_grad_ws(size_t rows, int C) { return C % 4 == 0 || C > 4 ? colred_workspace_bytes(rows, C) : 32; }
-
 // Dense layers whose width is not one the matrix-core kernels take (in % 4 or out % 4, beyond the small-output heads): one fp32 GEMM
 // C[m, n] = act(sum_k A(m, k) B(k, n) + bias[n]) with A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn], so the forward, the data gradient
 // (B = w read transposed) and the weight gradient (A = x read transposed) are the same kernel.  16 x 16 output tiles through LDS; each output is one
@@ -315,6 +275,12 @@ extern "C" {
 
 const char* gn_last_error(void) { return g_err; }
 int gn_version(void) { return 100; }
+
+// the device word every Philox kernel adds to its counter offset: what a captured hipGraph of a train step needs (a by-value argument is frozen at capture)
+int gn_set_rng_base(const uint64_t* base_dev) {
+  g_rng_base = base_dev;
+  return GN_OK;
+}
 
 int gn_prof_enable(int on) {
   g_prof_on = on != 0;
@@ -434,11 +400,6 @@ int gn_conv1d_fwd_dropout(const float* x, const float* w, const float* bias, con
   ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, act, act_param);
   a.mask = mask; a.keep_scale = 1.0f / (1.0f - rate);
   return conv_run(a, (hipStream_t)stream);
-}
-
-int gn_conv1d_transpose_w(const float* w, float* wt, int k, int Cin, int Cout, void* stream) {
-  GN_REQUIRE(w && wt && k >= 1 && Cin > 0 && Cout > 0, "transpose_w: bad arguments");
-  return transpose_w(w, wt, k, Cin, Cout, (hipStream_t)stream);
 }
 
 static int dgrad_impl(const float* dy, const float* wt, float* dx, int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, const float* gy,
@@ -564,31 +525,6 @@ int gn_conv1d_wgrad_any(const float* x, const float* dy, float* dw, float* db, v
   return wgrad_impl(x, dy, dw, db, ws, ws_bytes, B, L, Cin, Cout, k, stride, pad_left, Lout, true, stream);
 }
 
-int gn_conv2d_w2_fold(const float* w, const float* bias, float* wf, float* biasf, int kh, int Cin, int Cout, void* stream) {
-  GN_REQUIRE(w && wf && kh >= 1 && Cin > 0 && Cout > 0, "conv2d_w2_fold: bad arguments");
-  return conv2d_w2_fold(w, bias, wf, biasf, kh, Cin, Cout, (hipStream_t)stream);
-}
-int gn_conv2d_w2_unfold_grad(const float* dwf, const float* dbf, float* dw, float* db, int kh, int Cin, int Cout, void* stream) {
-  GN_REQUIRE(dwf && dw && kh >= 1 && Cin > 0 && Cout > 0, "conv2d_w2_unfold_grad: bad arguments");
-  return conv2d_w2_unfold(dwf, dbf, dw, db, kh, Cin, Cout, (hipStream_t)stream);
-}
-int gn_conv1d_up2_fold(const float* w, const float* bias, float* wf, float* biasf, int Cin, int Cout, int stride, void* stream) {
-  GN_REQUIRE(w && wf && Cin > 0 && Cout > 0 && (stride == 1 || stride == 2), "conv1d_up2_fold: bad arguments (5-tap 'same' conv, stride 1 or 2)");
-  return up2_fold(w, bias, wf, biasf, Cin, Cout, stride, (hipStream_t)stream);
-}
-int gn_conv1d_up2_unfold_grad(const float* dwf, const float* dbf, float* dw, float* db, int Cin, int Cout, int stride, void* stream) {
-  GN_REQUIRE(dwf && dw && Cin > 0 && Cout > 0 && (stride == 1 || stride == 2) && (!db || dbf), "conv1d_up2_unfold_grad: bad arguments");
-  return up2_unfold(dwf, dbf, dw, db, Cin, Cout, stride, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-size_t gn_bias_grad_workspace(size_t rows, int C) { return bias_grad_ws(rows, C) + 256; }
-
-int gn_bias_grad(const float* dy, float* db, void* ws, size_t ws_bytes, size_t rows, int C, void* stream) {
-  GN_REQUIRE(dy && db && ws && rows > 0 && C > 0, "bias_grad: bad arguments");
-  return bias_grad(dy, db, rows, C, ws, ws_bytes, (hipStream_t)stream);
-}
-
 int gn_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B, int in, int out, int act, float act_param, void* stream) {
   GN_REQUIRE(x && w && y && B >= 0 && in > 0 && out > 0, "dense_fwd: bad arguments");
   if (B == 0) return GN_OK;
@@ -642,233 +578,6 @@ int gn_dense_bwd(const float* x, const float* w, const float* dy, float* dx, flo
   if (rc) return rc;
   if (db) rc = bias_grad(dy, db, (size_t)B, out, ws2, ws2_bytes, s);
   return rc;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-int gn_act_fwd(const float* x, float* y, size_t n, int act, float p, void* stream) {
-  GN_REQUIRE(x && y, "act_fwd: null pointer");
-  return act_fwd(x, y, n, act, p, (hipStream_t)stream);
-}
-int gn_act_bwd(const float* dy, const float* y, float* dx, size_t n, int act, float p, void* stream) {
-  GN_REQUIRE(dy && y && dx, "act_bwd: null pointer");
-  return act_bwd(dy, y, dx, n, act, p, (hipStream_t)stream);
-}
-int gn_act_dropout_bwd(const float* dy, const float* y, const uint8_t* mask, float* dx, size_t n, int act, float p, float rate, void* stream) {
-  GN_REQUIRE(dy && y && mask && dx && rate >= 0.f && rate < 1.f, "act_dropout_bwd: bad arguments");
-  return act_dropout_bwd(dy, y, mask, dx, n, act, p, rate, (hipStream_t)stream);
-}
-int gn_dropout_mask(uint8_t* mask, size_t n, float rate, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(mask && rate >= 0.f && rate < 1.f, "dropout_mask: bad arguments");
-  return dropout_mask(mask, n, rate, seed, offset, (hipStream_t)stream);
-}
-int gn_dropout_apply(const float* x, const uint8_t* mask, float* y, size_t n, float rate, void* stream) {
-  GN_REQUIRE(x && mask && y && rate >= 0.f && rate < 1.f, "dropout_apply: bad arguments");
-  return dropout_apply(x, mask, y, n, rate, (hipStream_t)stream);
-}
-int gn_upsample2_fwd(const float* x, float* y, int B, int L, int C, void* stream) {
-  GN_REQUIRE(x && y, "upsample2_fwd: null pointer");
-  return upsample2_fwd(x, y, B, L, C, (hipStream_t)stream);
-}
-int gn_upsample2_bwd(const float* dy, float* dx, int B, int L, int C, void* stream) {
-  GN_REQUIRE(dy && dx, "upsample2_bwd: null pointer");
-  return upsample2_bwd(dy, dx, B, L, C, (hipStream_t)stream);
-}
-int gn_subtract_stack_fwd(const float* x, const float* event, float* img, int B, int n, void* stream) {
-  GN_REQUIRE(x && event && img, "subtract_stack_fwd: null pointer");
-  return subtract_stack_fwd(x, event, img, B, n, (hipStream_t)stream);
-}
-int gn_subtract_stack_bwd(const float* dimg, float* dx, int B, int n, void* stream) {
-  GN_REQUIRE(dimg && dx, "subtract_stack_bwd: null pointer");
-  return subtract_stack_bwd(dimg, dx, B, n, (hipStream_t)stream);
-}
-int gn_affine_stack_fwd(const float* x, const float* b0, const float* b1, float a0, float a1, float* img, int B, int n, void* stream) {
-  GN_REQUIRE(x && img && B >= 0 && n > 0, "affine_stack_fwd: bad arguments");
-  return affine_stack_fwd(x, b0, b1, a0, a1, img, B, n, (hipStream_t)stream);
-}
-int gn_affine_stack_bwd(const float* dimg, float a0, float a1, float* dx, int B, int n, void* stream) {
-  GN_REQUIRE(dimg && dx && B >= 0 && n > 0, "affine_stack_bwd: bad arguments");
-  return affine_stack_bwd(dimg, a0, a1, dx, B, n, (hipStream_t)stream);
-}
-int gn_assemble_d_batch(const float* real, const float* noise, const float* fake, const float* event, float* sX, int B, int n, void* stream) {
-  GN_REQUIRE(real && noise && fake && event && sX && B >= 0 && n > 0, "assemble_d_batch: bad arguments");
-  return assemble_d_batch(real, noise, fake, event, sX, B, n, (hipStream_t)stream);
-}
-int gn_fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(out, "fill_uniform: null pointer");
-  return fill_uniform(out, n, lo, hi, seed, offset, (hipStream_t)stream);
-}
-int gn_fill_normal(float* out, size_t n, float mean, float sd, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(out, "fill_normal: null pointer");
-  return fill_normal(out, n, mean, sd, seed, offset, (hipStream_t)stream);
-}
-int gn_gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE((x && y) || !n, "gaussian_noise_fwd: null pointer");
-  return gaussian_noise_fwd(x, y, n, stddev, seed, offset, (hipStream_t)stream);
-}
-int gn_gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE((x && y) || !n, "gaussian_dropout_apply: null pointer");
-  return gaussian_dropout_apply(x, y, n, sd, seed, offset, (hipStream_t)stream);
-}
-int gn_alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(((x && y) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_fwd: bad arguments");
-  return alpha_dropout_fwd(x, y, n, rate, a, b, alpha_p, seed, offset, (hipStream_t)stream);
-}
-int gn_alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(((dy && dx) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_bwd: bad arguments");
-  return alpha_dropout_bwd(dy, dx, n, rate, a, seed, offset, (hipStream_t)stream);
-}
-int gn_gather_rows(const float* src, const int64_t* idx, float* out, int rows, int width, void* stream) {
-  GN_REQUIRE(src && idx && out && rows >= 0 && width > 0, "gather_rows: bad arguments");
-  return gather_rows(src, idx, out, rows, width, (hipStream_t)stream);
-}
-int gn_axpy(float* y, const float* x, float a, size_t n, void* stream) {
-  GN_REQUIRE(y && x, "axpy: null pointer");
-  return axpy(y, x, a, n, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-size_t gn_bn_stats_workspace(size_t rows, int C) { return colred_workspace_bytes(rows, C) + 256; }
-
-int gn_bn_stats(const float* x, size_t rows, int C, double* sums, void* ws, size_t ws_bytes, void* stream) {
-  GN_REQUIRE(x && sums && ws && rows > 0 && C > 0, "bn_stats: bad arguments");
-  ColRedArgs r = {};
-  r.a = x; r.rows = rows; r.C = C;
-  return colred_run(1, r, ws, ws_bytes, sums, nullptr, (hipStream_t)stream);
-}
-int gn_bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum, float* moving_mean, float* moving_var,
-                   float* scale, float* shift, float* save_mean, float* save_invstd, int C, void* stream) {
-  GN_REQUIRE(sums && gamma && beta && scale && shift && save_mean && save_invstd && C > 0 && count > 1.0, "bn_finalize: bad arguments");
-  GN_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "bn_finalize: moving_mean/moving_var must both be given or both be NULL");
-  return bn_finalize(sums, count, gamma, beta, eps, momentum, moving_mean, moving_var, nullptr, nullptr, 0.f, scale, shift, save_mean, save_invstd, C,
-                     (hipStream_t)stream);
-}
-
-int gn_bn_finalize_zero_debias(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum, float* moving_mean,
-                               float* moving_var, float* biased_mean, float* biased_var, int local_step, float* scale, float* shift, float* save_mean,
-                               float* save_invstd, int C, void* stream) {
-  GN_REQUIRE(sums && gamma && beta && scale && shift && save_mean && save_invstd && C > 0 && count > 1.0, "bn_finalize_zero_debias: bad arguments");
-  GN_REQUIRE(moving_mean && moving_var && biased_mean && biased_var && local_step >= 1,
-             "bn_finalize_zero_debias: needs moving_mean/var, the biased accumulators and the incremented local_step (>= 1, got %d)", local_step);
-  return bn_finalize(sums, count, gamma, beta, eps, momentum, moving_mean, moving_var, biased_mean, biased_var, (float)local_step, scale, shift, save_mean,
-                     save_invstd, C, (hipStream_t)stream);
-}
-int gn_bn_infer_coeffs(const float* gamma, const float* beta, const float* moving_mean, const float* moving_var, float eps, float* scale, float* shift, int C,
-                       void* stream) {
-  GN_REQUIRE(gamma && beta && moving_mean && moving_var && scale && shift && C > 0, "bn_infer_coeffs: bad arguments");
-  return bn_infer_coeffs(gamma, beta, moving_mean, moving_var, eps, scale, shift, C, (hipStream_t)stream);
-}
-int gn_bn_apply(const float* x, const float* scale, const float* shift, const uint8_t* mask, float* y, size_t rows, int C, int act, float p, float rate,
-                void* stream) {
-  GN_REQUIRE(x && scale && shift && y && C > 0, "bn_apply: bad arguments");
-  GN_REQUIRE(rate >= 0.f && rate < 1.f && (mask || rate == 0.f), "bn_apply: dropout rate %f without mask", rate);
-  return bn_apply(x, scale, shift, mask, y, rows, C, act, p, mask ? rate : 0.f, (hipStream_t)stream);
-}
-int gn_bn_bwd_stats(const float* dy, const float* y, const float* x, const uint8_t* mask, const float* save_mean, const float* save_invstd, double* dsums, void* ws,
-                    size_t ws_bytes, size_t rows, int C, int act, float p, float rate, const float* scale, const float* shift, void* stream) {
-  GN_REQUIRE(dy && x && save_mean && save_invstd && dsums && ws && rows > 0 && C > 0, "bn_bwd_stats: bad arguments");
-  GN_REQUIRE((scale == nullptr) == (shift == nullptr) && (y || scale), "bn_bwd_stats: needs the layer output y, or scale AND shift to recompute it");
-  ColRedArgs r = {};
-  r.a = dy; r.y = y; r.xpre = x; r.mask = mask; r.mean = save_mean; r.invstd = save_invstd; r.scale = scale; r.shift = shift;
-  r.rows = rows; r.C = C; r.act = act; r.act_param = p; r.keep_scale = 1.0f / (1.0f - (mask ? rate : 0.f));
-  return colred_run(2, r, ws, ws_bytes, dsums, nullptr, (hipStream_t)stream);
-}
-int gn_bn_bwd_apply(const float* dy, const float* y, const float* x, const uint8_t* mask, const float* gamma, const float* save_mean, const float* save_invstd,
-                    const double* dsums_global, double count, const double* dsums_local, float* dx, float* dgamma, float* dbeta, size_t rows, int C, int act,
-                    float p, float rate, const float* scale, const float* shift, void* stream) {
-  GN_REQUIRE(dy && x && gamma && save_mean && save_invstd && dsums_global && dsums_local && dx && dgamma && dbeta && C > 0, "bn_bwd_apply: bad arguments");
-  GN_REQUIRE((scale == nullptr) == (shift == nullptr) && (y || scale), "bn_bwd_apply: needs the layer output y, or scale AND shift to recompute it");
-  return bn_bwd_apply(dy, y, x, mask, gamma, save_mean, save_invstd, dsums_global, count, dsums_local, dx, dgamma, dbeta, rows, C, act, p, mask ? rate : 0.f, scale,
-                      shift, (hipStream_t)stream);
-}
-
-static int lazy_dy_check(const char* who, const float* g, const float* w, int L, int Lout, int k, int pad_left, size_t rows, int C, const float* scale,
-                         const float* shift, LazyDy* z) {
-  GN_REQUIRE(g && w && L > 0 && Lout > 0 && k >= 1 && k <= 5 && pad_left >= 0, "%s: bad conv description (1 filter, 1..5 taps, stride 1)", who);
-  GN_REQUIRE(C % 4 == 0 && scale && shift, "%s: needs C %% 4 == 0 and the forward pass' scale / shift", who);
-  GN_REQUIRE(rows % (size_t)L == 0 && rows / (size_t)L < 0x7fffffffull, "%s: rows %zu is not a whole number of length-%d segments", who, rows, L);
-  z->g = g; z->w = w; z->L = L; z->Lout = Lout; z->k = k; z->pad_left = pad_left;
-  return GN_OK;
-}
-int gn_bn_bwd_stats_conv1(const float* g, const float* w, int L, int Lout, int k, int pad_left, const float* x, const uint8_t* mask, const float* save_mean,
-                          const float* save_invstd, double* dsums, void* ws, size_t ws_bytes, size_t rows, int C, int act, float p, float rate,
-                          const float* scale, const float* shift, void* stream) {
-  GN_REQUIRE(x && save_mean && save_invstd && dsums && ws && rows > 0 && C > 0, "bn_bwd_stats_conv1: bad arguments");
-  ColRedArgs r = {};
-  int rc = lazy_dy_check("bn_bwd_stats_conv1", g, w, L, Lout, k, pad_left, rows, C, scale, shift, &r.lz);
-  if (rc) return rc;
-  r.a = nullptr; r.y = nullptr; r.xpre = x; r.mask = mask; r.mean = save_mean; r.invstd = save_invstd; r.scale = scale; r.shift = shift;
-  r.rows = rows; r.C = C; r.act = act; r.act_param = p; r.keep_scale = 1.0f / (1.0f - (mask ? rate : 0.f));
-  return colred_run(2, r, ws, ws_bytes, dsums, nullptr, (hipStream_t)stream);
-}
-int gn_bn_bwd_apply_conv1(const float* g, const float* w, int L, int Lout, int k, int pad_left, const float* x, const uint8_t* mask, const float* gamma,
-                          const float* save_mean, const float* save_invstd, const double* dsums_global, double count, const double* dsums_local, float* dx,
-                          float* dgamma, float* dbeta, size_t rows, int C, int act, float p, float rate, const float* scale, const float* shift, void* stream) {
-  GN_REQUIRE(x && gamma && save_mean && save_invstd && dsums_global && dsums_local && dx && dgamma && dbeta && C > 0, "bn_bwd_apply_conv1: bad arguments");
-  LazyDy z = {};
-  int rc = lazy_dy_check("bn_bwd_apply_conv1", g, w, L, Lout, k, pad_left, rows, C, scale, shift, &z);
-  if (rc) return rc;
-  return bn_bwd_apply(nullptr, nullptr, x, mask, gamma, save_mean, save_invstd, dsums_global, count, dsums_local, dx, dgamma, dbeta, rows, C, act, p,
-                      mask ? rate : 0.f, scale, shift, (hipStream_t)stream, &z);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-int gn_bce_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream) {
-  GN_REQUIRE(p && y && dp && out, "bce_loss: null pointer");
-  return loss_run(0, p, y, dp, out, B, Bglobal, (hipStream_t)stream);
-}
-int gn_mse_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream) {
-  GN_REQUIRE(p && y && dp && out, "mse_loss: null pointer");
-  return loss_run(1, p, y, dp, out, B, Bglobal, (hipStream_t)stream);
-}
-int gn_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, void* stream) {
-  GN_REQUIRE(p && g && m && v, "adam_step: null pointer");
-  return adam_step(p, g, m, v, n, lr_t, b1, b2, eps, (hipStream_t)stream);
-}
-
-// ---- step-varying scalars from DEVICE memory: what a captured hipGraph of a train step needs (a by-value argument is frozen at capture) ----
-int gn_set_rng_base(const uint64_t* base_dev) {
-  g_rng_base = base_dev;
-  return GN_OK;
-}
-int gn_adam_step_dyn(float* p, const float* g, float* m, float* v, size_t n, const float* lr_t_dev, float b1, float b2, float eps, void* stream) {
-  GN_REQUIRE(p && g && m && v && lr_t_dev, "adam_step_dyn: null pointer");
-  return adam_step(p, g, m, v, n, 0.f, b1, b2, eps, (hipStream_t)stream, lr_t_dev);
-}
-int gn_optim_step(int rule, float* p, const float* g, float* s0, float* s1, float* s2, size_t n, float lr, const float* lr_dev, float h0, float h1,
-                  float eps, int nesterov, const float* clip_scale, float clipvalue, void* stream) {
-  GN_REQUIRE(rule >= GN_OPT_SGD && rule <= GN_OPT_AMSGRAD, "optim_step: unknown rule %d", rule);
-  if (!n) return GN_OK;
-  const int ns = rule == GN_OPT_AMSGRAD ? 3 : (rule == GN_OPT_ADADELTA || rule == GN_OPT_ADAMAX || rule == GN_OPT_ADAM) ? 2 : 1;
-  GN_REQUIRE(p && g && s0 && (ns < 2 || s1) && (ns < 3 || s2), "optim_step: null pointer (rule %d keeps %d state arrays)", rule, ns);
-  GN_REQUIRE(eps >= 0.f && clipvalue >= 0.f && h0 >= 0.f && h1 >= 0.f, "optim_step: negative hyper-parameter");
-  GN_REQUIRE(rule == GN_OPT_SGD || rule == GN_OPT_ADAGRAD || h0 <= 1.f, "optim_step: rho / beta_1 %g outside [0, 1]", h0);
-  GN_REQUIRE((rule != GN_OPT_ADAMAX && rule != GN_OPT_ADAM && rule != GN_OPT_AMSGRAD) || h1 <= 1.f, "optim_step: beta_2 %g outside [0, 1]", h1);
-  OptArgs a = {};
-  a.p = p; a.g = g; a.s0 = s0; a.s1 = ns > 1 ? s1 : nullptr; a.s2 = ns > 2 ? s2 : nullptr; a.n = n;
-  a.lr = lr; a.lr_dev = lr_dev; a.h0 = h0; a.h1 = h1; a.eps = eps; a.nesterov = nesterov ? 1 : 0; a.clip_scale = clip_scale; a.clipvalue = clipvalue;
-  return optim_step(rule, a, (hipStream_t)stream);
-}
-size_t gn_optim_sumsq_slots(size_t n) { return optim_sumsq_slots(n); }
-int gn_optim_sumsq(const float* g, size_t n, double* partials, void* stream) {
-  GN_REQUIRE(partials && (g || !n), "optim_sumsq: null pointer");
-  return optim_sumsq(g, n, partials, (hipStream_t)stream);
-}
-int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, void* stream) {
-  GN_REQUIRE(partials && factor && count > 0, "optim_clip_factor: null pointer or no partials");
-  GN_REQUIRE(clipnorm > 0.f, "optim_clip_factor: clipnorm %g must be > 0", clipnorm);
-  return optim_clip_factor(partials, count, clipnorm, factor, (hipStream_t)stream);
-}
-int gn_fill_normal_dyn(float* out, size_t n, float mean, const float* sd_dev, uint64_t seed, uint64_t offset, void* stream) {
-  GN_REQUIRE(out && sd_dev, "fill_normal_dyn: null pointer");
-  return fill_normal(out, n, mean, 0.f, seed, offset, (hipStream_t)stream, sd_dev);
-}
-int gn_bn_finalize_zero_debias_dyn(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum, float* moving_mean,
-                                   float* moving_var, float* biased_mean, float* biased_var, const int32_t* local_step_dev, float* scale, float* shift,
-                                   float* save_mean, float* save_invstd, int C, void* stream) {
-  GN_REQUIRE(sums && gamma && beta && scale && shift && save_mean && save_invstd && C > 0 && count > 1.0, "bn_finalize_zero_debias_dyn: bad arguments");
-  GN_REQUIRE(moving_mean && moving_var && biased_mean && biased_var && local_step_dev, "bn_finalize_zero_debias_dyn: needs moving statistics, accumulators, step");
-  return bn_finalize(sums, count, gamma, beta, eps, momentum, moving_mean, moving_var, biased_mean, biased_var, 1.f, scale, shift, save_mean, save_invstd, C,
-                     (hipStream_t)stream, local_step_dev);
 }
 
 }  // extern "C"

@@ -185,63 +185,15 @@ int wgrad_small_dispatch(WgradSmallArgs a, float* dw, size_t ws_bytes, hipStream
 int dense_small_fwd(const float* x, const float* w, const float* bias, float* y, int B, int in, int out, int act, float p, hipStream_t s);
 int dense_small_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int B, int in, int out, hipStream_t s,
                     int gact = 0, float gparam = 0.f, const uint8_t* gmask = nullptr, float gscale = 1.f);
-// elementwise.hip
-int act_fwd(const float* x, float* y, size_t n, int act, float p, hipStream_t s);
-int act_bwd(const float* dy, const float* y, float* dx, size_t n, int act, float p, hipStream_t s);
-int act_dropout_bwd(const float* dy, const float* y, const uint8_t* mask, float* dx, size_t n, int act, float p, float rate, hipStream_t s);
-int dropout_mask(uint8_t* mask, size_t n, float rate, uint64_t seed, uint64_t offset, hipStream_t s);
-int dropout_apply(const float* x, const uint8_t* mask, float* y, size_t n, float rate, hipStream_t s);
-int upsample2_fwd(const float* x, float* y, int B, int L, int C, hipStream_t s);
-int upsample2_bwd(const float* dy, float* dx, int B, int L, int C, hipStream_t s);
-int subtract_stack_fwd(const float* x, const float* ev, float* img, int B, int n, hipStream_t s);
-int subtract_stack_bwd(const float* dimg, float* dx, int B, int n, hipStream_t s);
-int affine_stack_fwd(const float* x, const float* b0, const float* b1, float a0, float a1, float* img, int B, int n, hipStream_t s);
-int affine_stack_bwd(const float* dimg, float a0, float a1, float* dx, int B, int n, hipStream_t s);
-int assemble_d_batch(const float* real, const float* noise, const float* fake, const float* ev, float* sX, int B, int n, hipStream_t s);
-int gather_rows(const float* src, const int64_t* idx, float* out, int rows, int width, hipStream_t s);
-int axpy(float* y, const float* x, float a, size_t n, hipStream_t s);
-int fill_uniform(float* out, size_t n, float lo, float hi, uint64_t seed, uint64_t offset, hipStream_t s);
-int fill_normal(float* out, size_t n, float mean, float sd, uint64_t seed, uint64_t offset, hipStream_t s, const float* sd_dev = nullptr);
-// noise_layers.hip
-int gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, hipStream_t s);
-int gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, hipStream_t s);
-int alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, hipStream_t s);
-int alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, hipStream_t s);
+// bn.hip: the fixed-order fp64 column reduction (BatchNorm statistics, bias gradients, the convolutions' statistics epilogues)
 size_t colred_workspace_bytes(size_t rows, int C);
 int colred_run(int mode, ColRedArgs a, void* ws, size_t ws_bytes, double* out_f64, float* out_f32, hipStream_t s);
 int colred_finalize(const double* part, double* out_f64, size_t n, int chunks, hipStream_t s);   // out[i] = sum_k part[k*n + i], fixed order
 int colred_finalize_f32(const double* part, float* out_f32, size_t n, int chunks, hipStream_t s);
-int bn_finalize(const double* sums, double count, const float* gamma, const float* beta, float eps, float momentum, float* mm, float* mv,
-                float* bm, float* bv, float zd_step, float* scale, float* shift, float* smean, float* sinv, int C, hipStream_t s,
-                const int32_t* zd_step_dev = nullptr);
-int bn_infer_coeffs(const float* gamma, const float* beta, const float* mm, const float* mv, float eps, float* scale, float* shift, int C, hipStream_t s);
-int bn_apply(const float* x, const float* scale, const float* shift, const uint8_t* mask, float* y, size_t rows, int C, int act, float p, float rate, hipStream_t s);
-int bn_bwd_apply(const float* dy, const float* y, const float* x, const uint8_t* mask, const float* gamma, const float* mean, const float* invstd,
-                 const double* dsums_global, double count, const double* dsums_local, float* dx, float* dgamma, float* dbeta, size_t rows, int C,
-                 int act, float p, float rate, const float* scale, const float* shift, hipStream_t s, const LazyDy* lz = nullptr);
-int loss_run(int kind, const float* p, const float* y, float* dp, float* out, int B, int Bglobal, hipStream_t s);
-int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, hipStream_t s, const float* lr_t_dev = nullptr);
-// optim.hip
-struct OptArgs {
-  float *p, *s0, *s1, *s2;      // parameters and up to three state arrays (the rule's own: m | a | a, d | m, u | m, v | m, v, vhat)
-  const float* g;
-  size_t n;
-  float lr;                     // lr_eff or lr_t of this step, unless lr_dev is set (captured step: read at run time)
-  const float* lr_dev;
-  float h0, h1, eps;            // momentum | rho | beta_1, beta_2
-  int nesterov;
-  const float* clip_scale;      // clipnorm / norm (or 1) in device memory; null: no clip norm
-  float clipvalue;              // > 0: clip g to [-clipvalue, clipvalue] after the clip-norm scale
-};
-int optim_step(int rule, const OptArgs& a, hipStream_t s);
-size_t optim_sumsq_slots(size_t n);
-int optim_sumsq(const float* g, size_t n, double* partials, hipStream_t s);
-int optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, hipStream_t s);
+size_t bias_grad_ws(size_t rows, int C);
+int bias_grad(const float* dy, float* db, size_t rows, int C, void* ws, size_t ws_bytes, hipStream_t s);      // db[c] = sum over rows of dy[row, c]
+// weight_layout.hip
 int transpose_w(const float* w, float* wt, int k, int Cin, int Cout, hipStream_t s);
-int conv2d_w2_fold(const float* w, const float* bias, float* wf, float* bf, int kh, int Cin, int Cout, hipStream_t s);
-int conv2d_w2_unfold(const float* dwf, const float* dbf, float* dw, float* db, int kh, int Cin, int Cout, hipStream_t s);
-int up2_fold(const float* w, const float* bias, float* wf, float* bf, int Cin, int Cout, int stride, hipStream_t s);
-int up2_unfold(const float* dwf, const float* dbf, float* dw, float* db, int Cin, int Cout, int stride, hipStream_t s);
 
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 // grid of the streaming (HBM-bound) grid-stride kernels: one thread per item up to ~8 blocks of 256 per CU

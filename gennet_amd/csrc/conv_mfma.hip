@@ -506,7 +506,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
   return full ? launch_conv_impl<WM, WN, WAVES_M, WAVES_N, KC, NTAPS, true>(a, s) : launch_conv_impl<WM, WN, WAVES_M, WAVES_N, KC, NTAPS, false>(a, s);
 }
 
-// Entry used by the C-ABI wrappers in capi.hip.
+// Entry used by the convolution and Dense entry points in capi.hip.
 int conv_mfma_dispatch(const ConvArgs& a, hipStream_t s) {
   if (a.Cin % 4 || a.Cout % 4) {
     set_error("conv_mfma: Cin (%d) and Cout (%d) must be multiples of 4", a.Cin, a.Cout);

@@ -36,7 +36,7 @@ __device__ __forceinline__ double loss_one_minus_eps() { return (double)(1.f - 1
 template <int K>
 __device__ __forceinline__ void loss_term(float pf, float yf, double& t, double& g) {
   const double p = (double)pf, y = (double)yf, d = p - y, eps = loss_eps();
-  if (K == GN_LOSS_BINARY_CROSSENTROPY) {        // as loss_kernel<0> (elementwise.hip): TF's sigmoid cross-entropy on the logit of the clipped p
+  if (K == GN_LOSS_BINARY_CROSSENTROPY) {        // as loss_kernel<0> (below): TF's sigmoid cross-entropy on the logit of the clipped p
     const double pc = fmin(fmax(p, eps), loss_one_minus_eps());
     const double z = log(pc / (1.0 - pc));
     t = fmax(z, 0.0) - z * y + log1p(exp(-fabs(z)));
@@ -476,6 +476,47 @@ static void loss_launch_row_weighted(const LossShape& sh, const float* p, const 
   else hipLaunchKernelGGL((loss_row_weighted_kernel<K, false>), dim3(sh.blocks), dim3(256), 0, s, p, y, dp, rows, cols, sh.rpg, sh.wave, w, count, partials);
 }
 
+// ---------------------------------------------------------------------------------------------
+// the original BCE / MSE losses on a (B, 1) output: single block (B is a batch size, a few thousand at most).  Kept beside the pass above
+// for their bits: ops.LOSS_PASS_MIN_ELEMENTS routes small batches here
+// ---------------------------------------------------------------------------------------------
+template <int KIND>  // 0 = BCE, 1 = MSE
+__global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ p, const float* __restrict__ y, float* __restrict__ dp, float* __restrict__ out,
+                                                   int B, int Bglobal) {
+  const float eps = 1e-7f;
+  float lsum = 0.f, hits = 0.f;
+  for (int i = threadIdx.x; i < B; i += 256) {
+    const float pv = p[i], yv = y[i];
+    if (KIND == 0) {
+      const float pc = fminf(fmaxf(pv, eps), 1.f - eps);
+      const float z = logf(pc / (1.f - pc));
+      lsum += fmaxf(z, 0.f) - z * yv + log1pf(expf(-fabsf(z)));
+      const bool inside = (pv >= eps) && (pv <= 1.f - eps);
+      const float sg = 1.f / (1.f + expf(-z));
+      dp[i] = inside ? (sg - yv) / (pc * (1.f - pc)) / (float)Bglobal : 0.f;
+    } else {
+      const float d = pv - yv;
+      lsum += d * d;
+      dp[i] = 2.f * d / (float)Bglobal;
+    }
+    hits += (rintf(pv) == yv) ? 1.f : 0.f;
+  }
+  __shared__ float r0[256], r1[256];
+  r0[threadIdx.x] = lsum; r1[threadIdx.x] = hits;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) { r0[threadIdx.x] += r0[threadIdx.x + sft]; r1[threadIdx.x] += r1[threadIdx.x + sft]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = r0[0] / (float)Bglobal; out[1] = r1[0]; }
+}
+static int loss_run(int kind, const float* p, const float* y, float* dp, float* out, int B, int Bglobal, hipStream_t s) {
+  GN_REQUIRE(B >= 1 && Bglobal >= B, "loss: bad batch sizes %d / %d", B, Bglobal);
+  if (kind == 0) hipLaunchKernelGGL(loss_kernel<0>, dim3(1), dim3(256), 0, s, p, y, dp, out, B, Bglobal);
+  else hipLaunchKernelGGL(loss_kernel<1>, dim3(1), dim3(256), 0, s, p, y, dp, out, B, Bglobal);
+  return check_launch("loss");
+}
+
 }  // namespace gn
 
 extern "C" size_t gn_loss_pass_workspace(long long rows, int cols) {
@@ -610,4 +651,13 @@ extern "C" int gn_loss_pass_weighted(int kind, const float* p, const float* y, c
   if (rc) return rc;
   hipLaunchKernelGGL(loss_finish_weighted_kernel, dim3(1), dim3(256), 0, s, (const double*)partials, (int)sh.blocks, count, coldiv, (double)cols, out);
   return check_launch("loss_finish_weighted");
+}
+
+extern "C" int gn_bce_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream) {
+  GN_REQUIRE(p && y && dp && out, "bce_loss: null pointer");
+  return gn::loss_run(0, p, y, dp, out, B, Bglobal, (hipStream_t)stream);
+}
+extern "C" int gn_mse_loss(const float* p, const float* y, float* dp, float* out, int B, int Bglobal, void* stream) {
+  GN_REQUIRE(p && y && dp && out, "mse_loss: null pointer");
+  return gn::loss_run(1, p, y, dp, out, B, Bglobal, (hipStream_t)stream);
 }

@@ -71,17 +71,27 @@ static int noise_launch(const char* what, const float* x, float* y, size_t n, fl
   return check_launch(what);
 }
 
-int gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, hipStream_t s) {
-  return noise_launch<NOISE_ADD>("gaussian_noise_fwd", x, y, n, stddev, 0.f, 0.f, 0.f, seed, offset, s);
+}  // namespace gn
+
+using namespace gn;
+
+extern "C" {
+
+int gn_gaussian_noise_fwd(const float* x, float* y, size_t n, float stddev, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE((x && y) || !n, "gaussian_noise_fwd: null pointer");
+  return noise_launch<NOISE_ADD>("gaussian_noise_fwd", x, y, n, stddev, 0.f, 0.f, 0.f, seed, offset, (hipStream_t)stream);
 }
-int gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, hipStream_t s) {
-  return noise_launch<NOISE_MUL>("gaussian_dropout_apply", x, y, n, sd, 0.f, 0.f, 0.f, seed, offset, s);
+int gn_gaussian_dropout_apply(const float* x, float* y, size_t n, float sd, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE((x && y) || !n, "gaussian_dropout_apply: null pointer");
+  return noise_launch<NOISE_MUL>("gaussian_dropout_apply", x, y, n, sd, 0.f, 0.f, 0.f, seed, offset, (hipStream_t)stream);
 }
-int alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, hipStream_t s) {
-  return noise_launch<ALPHA_FWD>("alpha_dropout_fwd", x, y, n, a, b, alpha_p, rate, seed, offset, s);
+int gn_alpha_dropout_fwd(const float* x, float* y, size_t n, float rate, float a, float b, float alpha_p, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE(((x && y) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_fwd: bad arguments");
+  return noise_launch<ALPHA_FWD>("alpha_dropout_fwd", x, y, n, a, b, alpha_p, rate, seed, offset, (hipStream_t)stream);
 }
-int alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, hipStream_t s) {
-  return noise_launch<ALPHA_BWD>("alpha_dropout_bwd", dy, dx, n, a, 0.f, 0.f, rate, seed, offset, s);
+int gn_alpha_dropout_bwd(const float* dy, float* dx, size_t n, float rate, float a, uint64_t seed, uint64_t offset, void* stream) {
+  GN_REQUIRE(((dy && dx) || !n) && rate > 0.f && rate < 1.f, "alpha_dropout_bwd: bad arguments");
+  return noise_launch<ALPHA_BWD>("alpha_dropout_bwd", dy, dx, n, a, 0.f, 0.f, rate, seed, offset, (hipStream_t)stream);
 }
 
-}  // namespace gn
+}  // extern "C"

@@ -1,5 +1,6 @@
-// Keras 2.2.4 optimizers beyond the default Adam pass (SGD, RMSprop, Adagrad, Adadelta, Adamax, Adam with decay / amsgrad / clipping):
-// one fused HBM-bound update pass templated on the rule, and the deterministic clip-norm reduction in front of it.
+// Keras 2.2.4 optimizers: the default Adam pass (adam_kernel, the engine's own update), the other rules (SGD, RMSprop, Adagrad, Adadelta,
+// Adamax, Adam with decay / amsgrad / clipping) as one fused HBM-bound update pass templated on the rule, and the deterministic clip-norm
+// reduction in front of it.
 //
 //  * optim_kernel<RULE>: reads p, g and the rule's state once, writes p and the state once (float4 body, scalar head / tail for any
 //    length and alignment).  g is scaled by the clip-norm factor (device memory) and clipped to +-clipvalue first, Keras' order.
@@ -10,6 +11,18 @@
 #include "common.h"
 
 namespace gn {
+
+struct OptArgs {
+  float *p, *s0, *s1, *s2;      // parameters and up to three state arrays (the rule's own: m | a | a, d | m, u | m, v | m, v, vhat)
+  const float* g;
+  size_t n;
+  float lr;                     // lr_eff or lr_t of this step, unless lr_dev is set (captured step: read at run time)
+  const float* lr_dev;
+  float h0, h1, eps;            // momentum | rho | beta_1, beta_2
+  int nesterov;
+  const float* clip_scale;      // clipnorm / norm (or 1) in device memory; null: no clip norm
+  float clipvalue;              // > 0: clip g to [-clipvalue, clipvalue] after the clip-norm scale
+};
 
 struct OptK {
   float lr, h0, h1, om0, om1, eps, scale, clipvalue;
@@ -106,24 +119,6 @@ static size_t vec_head(size_t n, std::initializer_list<const void*> ptrs) {
   return h < n ? h : n;
 }
 
-int optim_step(int rule, const OptArgs& a, hipStream_t s) {
-  if (!a.n) return GN_OK;
-  const size_t head = vec_head(a.n, {a.p, a.g, a.s0, a.s1, a.s2});
-  const size_t nvec = (a.n - head) / 4;
-  const dim3 grid(stream_grid(nvec ? nvec : a.n)), block(256);
-  switch (rule) {
-    case GN_OPT_SGD: hipLaunchKernelGGL(optim_kernel<GN_OPT_SGD>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_RMSPROP: hipLaunchKernelGGL(optim_kernel<GN_OPT_RMSPROP>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_ADAGRAD: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAGRAD>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_ADADELTA: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADADELTA>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_ADAMAX: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAMAX>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_ADAM: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAM>, grid, block, 0, s, a, head, nvec); break;
-    case GN_OPT_AMSGRAD: hipLaunchKernelGGL(optim_kernel<GN_OPT_AMSGRAD>, grid, block, 0, s, a, head, nvec); break;
-    default: set_error("optim_step: unknown rule %d", rule); return GN_EINVAL;
-  }
-  return check_launch("optim_step");
-}
-
 // ---------------------------------------------------------------------------------------------
 // clip norm: fixed-slot fp64 partials, fixed-order finalize
 // ---------------------------------------------------------------------------------------------
@@ -156,18 +151,6 @@ __global__ __launch_bounds__(256) void optim_sumsq_kernel(const float* __restric
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-size_t optim_sumsq_slots(size_t n) {
-  const size_t b = cdiv(n / 4 + 1, 256);
-  return b < 1 ? 1 : (b > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : b);
-}
-
-int optim_sumsq(const float* g, size_t n, double* partials, hipStream_t s) {
-  const size_t head = vec_head(n, {g});
-  const size_t nvec = (n - head) / 4;
-  hipLaunchKernelGGL(optim_sumsq_kernel, dim3((unsigned)optim_sumsq_slots(n)), dim3(256), 0, s, g, n, head, nvec, partials);
-  return check_launch("optim_sumsq");
-}
-
 __global__ __launch_bounds__(256) void optim_clip_factor_kernel(const double* __restrict__ partials, size_t count, float clipnorm, float* __restrict__ factor) {
   double acc = 0.0;
   for (size_t i = threadIdx.x; i < count; i += 256) acc += partials[i];
@@ -178,9 +161,86 @@ __global__ __launch_bounds__(256) void optim_clip_factor_kernel(const double* __
   }
 }
 
-int optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, hipStream_t s) {
-  hipLaunchKernelGGL(optim_clip_factor_kernel, dim3(1), dim3(256), 0, s, partials, count, clipnorm, factor);
-  return check_launch("optim_clip_factor");
+// ---------------------------------------------------------------------------------------------
+// the default Adam (keras form), one fused pass over the flat parameter segment; lr_t by value, or from device memory for a captured step
+// ---------------------------------------------------------------------------------------------
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr_t, float b1,
+                            float b2, float eps, const float* __restrict__ lr_t_dev) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  if (lr_t_dev) lr_t = *lr_t_dev;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float gi = g[i];
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+  }
+}
+static int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, const float* lr_t_dev, float b1, float b2, float eps, hipStream_t s) {
+  if (!n) return GN_OK;
+  hipLaunchKernelGGL(adam_kernel, dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, lr_t_dev);
+  return check_launch("adam");
 }
 
 }  // namespace gn
+
+using namespace gn;
+
+extern "C" {
+
+int gn_optim_step(int rule, float* p, const float* g, float* s0, float* s1, float* s2, size_t n, float lr, const float* lr_dev, float h0, float h1,
+                  float eps, int nesterov, const float* clip_scale, float clipvalue, void* stream) {
+  GN_REQUIRE(rule >= GN_OPT_SGD && rule <= GN_OPT_AMSGRAD, "optim_step: unknown rule %d", rule);
+  if (!n) return GN_OK;
+  const int ns = rule == GN_OPT_AMSGRAD ? 3 : (rule == GN_OPT_ADADELTA || rule == GN_OPT_ADAMAX || rule == GN_OPT_ADAM) ? 2 : 1;
+  GN_REQUIRE(p && g && s0 && (ns < 2 || s1) && (ns < 3 || s2), "optim_step: null pointer (rule %d keeps %d state arrays)", rule, ns);
+  GN_REQUIRE(eps >= 0.f && clipvalue >= 0.f && h0 >= 0.f && h1 >= 0.f, "optim_step: negative hyper-parameter");
+  GN_REQUIRE(rule == GN_OPT_SGD || rule == GN_OPT_ADAGRAD || h0 <= 1.f, "optim_step: rho / beta_1 %g outside [0, 1]", h0);
+  GN_REQUIRE((rule != GN_OPT_ADAMAX && rule != GN_OPT_ADAM && rule != GN_OPT_AMSGRAD) || h1 <= 1.f, "optim_step: beta_2 %g outside [0, 1]", h1);
+  OptArgs a = {};
+  a.p = p; a.g = g; a.s0 = s0; a.s1 = ns > 1 ? s1 : nullptr; a.s2 = ns > 2 ? s2 : nullptr; a.n = n;
+  a.lr = lr; a.lr_dev = lr_dev; a.h0 = h0; a.h1 = h1; a.eps = eps; a.nesterov = nesterov ? 1 : 0; a.clip_scale = clip_scale; a.clipvalue = clipvalue;
+  const size_t head = vec_head(a.n, {a.p, a.g, a.s0, a.s1, a.s2});
+  const size_t nvec = (a.n - head) / 4;
+  const dim3 grid(stream_grid(nvec ? nvec : a.n)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  switch (rule) {
+    case GN_OPT_SGD: hipLaunchKernelGGL(optim_kernel<GN_OPT_SGD>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_RMSPROP: hipLaunchKernelGGL(optim_kernel<GN_OPT_RMSPROP>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_ADAGRAD: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAGRAD>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_ADADELTA: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADADELTA>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_ADAMAX: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAMAX>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_ADAM: hipLaunchKernelGGL(optim_kernel<GN_OPT_ADAM>, grid, block, 0, s, a, head, nvec); break;
+    case GN_OPT_AMSGRAD: hipLaunchKernelGGL(optim_kernel<GN_OPT_AMSGRAD>, grid, block, 0, s, a, head, nvec); break;
+  }
+  return check_launch("optim_step");
+}
+
+size_t gn_optim_sumsq_slots(size_t n) {
+  const size_t b = cdiv(n / 4 + 1, 256);
+  return b < 1 ? 1 : (b > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : b);
+}
+int gn_optim_sumsq(const float* g, size_t n, double* partials, void* stream) {
+  GN_REQUIRE(partials && (g || !n), "optim_sumsq: null pointer");
+  const size_t head = vec_head(n, {g});
+  const size_t nvec = (n - head) / 4;
+  hipLaunchKernelGGL(optim_sumsq_kernel, dim3((unsigned)gn_optim_sumsq_slots(n)), dim3(256), 0, (hipStream_t)stream, g, n, head, nvec, partials);
+  return check_launch("optim_sumsq");
+}
+int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, void* stream) {
+  GN_REQUIRE(partials && factor && count > 0, "optim_clip_factor: null pointer or no partials");
+  GN_REQUIRE(clipnorm > 0.f, "optim_clip_factor: clipnorm %g must be > 0", clipnorm);
+  hipLaunchKernelGGL(optim_clip_factor_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, count, clipnorm, factor);
+  return check_launch("optim_clip_factor");
+}
+
+int gn_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps, void* stream) {
+  GN_REQUIRE(p && g && m && v, "adam_step: null pointer");
+  return adam_step(p, g, m, v, n, lr_t, nullptr, b1, b2, eps, (hipStream_t)stream);
+}
+int gn_adam_step_dyn(float* p, const float* g, float* m, float* v, size_t n, const float* lr_t_dev, float b1, float b2, float eps, void* stream) {
+  GN_REQUIRE(p && g && m && v && lr_t_dev, "adam_step_dyn: null pointer");
+  return adam_step(p, g, m, v, n, 0.f, lr_t_dev, b1, b2, eps, (hipStream_t)stream);
+}
+
+}  // extern "C"

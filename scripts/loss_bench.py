@@ -1,4 +1,4 @@
-"""The one-block loss kernel (gn_mse_loss, csrc/elementwise.hip) against the streaming loss pass (gn_loss_pass, csrc/loss.hip) for
+"""The one-block loss kernel (gn_mse_loss, loss_kernel in csrc/loss.hip) against the streaming loss pass (gn_loss_pass, the same file) for
 mean_squared_error at 2^10 .. 2^22 elements: where the engine should switch from the first to the second (ops.LOSS_PASS_MIN_ELEMENTS).
 
 Both are called through the C ABI on preallocated buffers, so what lies between the device events is the launches alone: `--warmup` calls of

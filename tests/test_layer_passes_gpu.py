@@ -4,7 +4,9 @@ and float4 tail, the one-block losses, and the device-scalar variants of three e
 tests/layer_ref.py (fp64 numpy on the fp32 inputs).  Conventions (g / f32 / close) and tolerances are those of test_kernels_gpu.py: 2e-5
 of the largest oracle magnitude for outputs and data gradients (fp32 fmaf chains of up to 4100 terms), 5e-5 for weight / bias gradients.
 
-Which case reaches which seam (gennet_amd/csrc: capi.hip gn_dense_fwd / gn_dense_bwd, small_conv.hip, elementwise.hip).  The matrix-core
+Which case reaches which seam (gennet_amd/csrc: capi.hip gn_dense_fwd / gn_dense_bwd, small_conv.hip; bn.hip for the column reductions, the bias
+gradients and the BatchNormalization passes, elementwise.hip for the streaming passes, loss.hip for the one-block losses, optim.hip for
+Adam).  The matrix-core
 route is asserted with the launch counters; the small head and the any-shape GEMM have no counter (the tests only assert that they launch no
 counted kernel), so which of the two a shape takes is read off gn_dense_fwd / gn_dense_bwd: dense_any_shape(in, out) first, then out <= 4.
 

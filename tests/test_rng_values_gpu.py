@@ -3,7 +3,8 @@ known-answer vectors by tests/test_philox_ref_cpu.py).  The other RNG tests comp
 equal fill_normal / dropout_mask, moments); here a wrong round count, a dropped high word of counter or seed, a wrong Weyl constant, a wrong
 shift in u01_24, swapped Box-Muller lanes, `>` for `>=` or an ignored stream base changes a compared value.
 
-Which case reaches what (gennet_amd/csrc: common.h, elementwise.hip, noise_layers.hip, bn_dropgen.hip, synth.hip, noise_chain.h, synth_fused.hip)
+Which case reaches what (gennet_amd/csrc: common.h, elementwise.hip for the fills and the dropout mask, noise_layers.hip, bn_dropgen.hip,
+synth.hip, noise_chain.h, synth_fused.hip)
 
 Element-wise draws (fill_uniform, dropout_mask, fill_normal: one thread per counter = 4 elements, grid capped at 2048 blocks of 256 = 2^19 threads)
     n 1, 3                  one counter, tail stores only           n 4   one full counter (the mask's dword store), no tail
