@@ -7,6 +7,7 @@
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
+    from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -38,6 +39,17 @@ def _unused(where, *names):
     return dict((n, _placeholder(n, 'bbhMahoGANy.py:' + where)) for n in names)
 
 
+def _pooling_placeholder(name, where):
+    """MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D under the names bbhMahoGANy.py imports and never instantiates: the real classes are
+    gennet_amd.layers.<Name> (= gennet_amd.keras.layers.pooling.<Name>, and what load_model builds); these import-line names keep refusing."""
+    def __init__(self, *a, **k):
+        raise NotImplementedError('%s under this name is the import of bbhMahoGANy.py:%s, which the script never instantiates, and it keeps refusing so '
+                                  'that a script which starts to use it is noticed; the layer itself is gennet_amd.layers.%s (also '
+                                  'gennet_amd.keras.layers.pooling.%s, and what load_model / model_from_json build)' % (name, where, name, name))
+    return type(name, (object,), {'__init__': __init__, '__doc__': 'placeholder for the unused import of keras %s; the layer is gennet_amd.layers.%s'
+                                                                   % (name, name)})
+
+
 def _pick(mod, *names):
     return dict((n, getattr(mod, n)) for n in names)
 
@@ -45,13 +57,17 @@ def _pick(mod, *names):
 _core = _pick(_layers, 'Activation', 'Dense', 'Dropout', 'Flatten', 'Reshape')
 _norm = _pick(_layers, 'BatchNormalization')
 _conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'UpSampling1D', 'MaxPooling2D'),
-             **_unused('37-38', 'UpSampling2D', 'AveragePooling1D', 'MaxPooling1D'))
+             **_unused('37-38', 'UpSampling2D'))
+_conv.update((n, _pooling_placeholder(n, '37-38')) for n in ('AveragePooling1D', 'MaxPooling1D'))
+_pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'AveragePooling2D', 'GlobalAveragePooling1D', 'GlobalAveragePooling2D',
+                 'GlobalMaxPooling1D', 'GlobalMaxPooling2D')
 _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU'), **_unused('39', 'ThresholdedReLU'))
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
-_top.update(_unused('33-34', 'GlobalAveragePooling1D'))
+_top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
+_top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))
 for _d in (_core, _norm, _conv, _act, _noise):
-    _top.update((k, v) for k, v in _d.items() if k in _layers.__dict__)
+    _top.update((k, v) for k, v in _d.items() if v is _layers.__dict__.get(k))
 
 _TREE = {
     'models': _pick(_engine, 'Model', 'Sequential', 'load_model', 'model_from_json'),
@@ -64,6 +80,7 @@ _TREE = {
     'layers.convolutional': _conv,
     'layers.advanced_activations': _act,
     'layers.noise': _noise,
+    'layers.pooling': _pooling,
     'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
     'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }

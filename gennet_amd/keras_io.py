@@ -215,8 +215,10 @@ def layer_config(layer):
         cfg.update(data_format='channels_last')
     elif isinstance(layer, L.UpSampling1D):
         cfg.update(size=2)
-    elif isinstance(layer, L.MaxPooling2D):
-        cfg.update(pool_size=[2, 1], padding='valid', strides=[2, 1], data_format='channels_last')
+    elif isinstance(layer, L._Pooling):          # keras 2.2.4 layers/pooling.py: lists of length 1 (1-D) or 2 (2-D)
+        cfg.update(pool_size=list(layer.pool_size), padding=layer.padding, strides=list(layer.strides), data_format='channels_last')
+    elif isinstance(layer, L._GlobalPooling):
+        cfg.update(data_format='channels_last')
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -316,8 +318,12 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.Flatten(**kw)
     if class_name == 'UpSampling1D':
         return L.UpSampling1D(size=cfg.get('size', 2), **kw)
-    if class_name == 'MaxPooling2D':
-        return L.MaxPooling2D(pool_size=tuple(cfg.get('pool_size', (2, 2))), strides=cfg.get('strides'), padding=cfg.get('padding', 'valid'), **kw)
+    if class_name in ('MaxPooling2D', 'AveragePooling2D', 'MaxPooling1D', 'AveragePooling1D'):
+        # data_format: absent in the 1-D configs of older keras; 'channels_first' is refused by the layer
+        return getattr(L, class_name)(pool_size=cfg.get('pool_size'), strides=cfg.get('strides'), padding=cfg.get('padding', 'valid'),
+                                      data_format=cfg.get('data_format'), **kw)
+    if class_name in ('GlobalAveragePooling1D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'):
+        return getattr(L, class_name)(data_format=cfg.get('data_format'), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 

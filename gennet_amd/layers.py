@@ -910,29 +910,144 @@ class UpSampling1D(Layer):
         return ops.upsample2_bwd(dy.contiguous())
 
 
-class MaxPooling2D(Layer):
-    """bbhMahoGANy.py:444, :453, :462, ... (`maxpool = True`): MaxPooling2D(pool_size=(2,1)) -- pairs of rows along H; strides = pool_size, 'valid'."""
+def _pool_tuple(v, rank, what):
+    t = (int(v),) * rank if isinstance(v, (int, np.integer)) and not isinstance(v, bool) else tuple(int(u) for u in v)
+    if len(t) != rank or any(u < 1 for u in t):
+        raise ValueError('%s %r: %d positive integer%s' % (what, v, rank, '' if rank == 1 else 's'))
+    return t
 
-    def __init__(self, pool_size=(2, 2), strides=None, padding='valid', **kw):
+
+class _Pooling(Layer):
+    """Keras 2.2.4 layers/pooling.py on the passes of csrc/pooling.hip: channels_last, any pool_size, strides (None: the pool size) and
+    padding 'valid' | 'same'.  The 1-D layers run as (B, L, 1, C).  An ordinary layer for the planner: it absorbs nothing and nothing absorbs it.
+    The tape keeps x for the maximum in the training phase, shapes only for the average."""
+    mode, rank = None, 2
+
+    def __init__(self, pool_size=None, strides=None, padding='valid', data_format=None, **kw):
         Layer.__init__(self, **kw)
-        pool_size = (pool_size, pool_size) if isinstance(pool_size, int) else tuple(pool_size)
-        strides = pool_size if strides is None else ((strides, strides) if isinstance(strides, int) else tuple(strides))
-        if pool_size != (2, 1) or strides != (2, 1) or padding != 'valid':
-            raise NotImplementedError('MaxPooling2D is implemented for the reference\'s case only: pool_size (2,1), strides (2,1), padding "valid"')
+        name = type(self).__name__
+        if pool_size is None:
+            pool_size = 2
+        if data_format not in (None, 'channels_last'):
+            raise NotImplementedError('%s(data_format=%r): channels_last only' % (name, data_format))
+        if padding not in ('valid', 'same'):
+            raise ValueError("%s(padding=%r): 'valid' or 'same'" % (name, padding))
+        self.pool_size = _pool_tuple(pool_size, self.rank, '%s(pool_size)' % name)
+        self.strides = self.pool_size if strides is None else _pool_tuple(strides, self.rank, '%s(strides)' % name)
+        self.padding = padding
+        # the discriminator's `maxpool = True` layers keep their own two kernels (csrc/pool.hip): same kernels, same launches
+        self.h2 = self.mode == 'max' and self.rank == 2 and self.pool_size == (2, 1) and self.strides == (2, 1) and padding == 'valid'
+
+    def _pool2(self):
+        return (self.pool_size + (1,))[:2], (self.strides + (1,))[:2]
 
     def compute_output_shape(self, input_shape):
-        if input_shape[0] < 2:
-            raise ValueError('MaxPooling2D(pool_size=(2,1)) on %d rows' % input_shape[0])
-        return (input_shape[0] // 2,) + tuple(input_shape[1:])
+        if len(input_shape) != self.rank + 1:
+            raise ValueError('%s expects (batch, %s, channels) inputs, got %r' % (type(self).__name__, 'steps' if self.rank == 1 else 'rows, cols',
+                                                                                 (None,) + tuple(input_shape)))
+        out =tuple(ops.pool_geometry(n, p, s, self.padding)[0] for n, p, s in zip(input_shape, self.pool_size, self.strides))
+        return out + (input_shape[-1],)
 
     def forward(self, ctx, node, x):
         x = x.contiguous()
+        if self.h2:
+            if ctx.training:
+                ctx.tape[node.index] = x
+            return ops.maxpool_h2_fwd(x)
+        x4 = x if self.rank == 2 else x.unsqueeze(2)
         if ctx.training:
-            ctx.tape[node.index] = x
-        return ops.maxpool_h2_fwd(x)
+            ctx.tape[node.index] = (x4 if self.mode == 'max' else None, tuple(x4.shape))
+        pool, strides = self._pool2()
+        y = ops.pool2d_fwd(self.mode, x4, pool, strides, self.padding)
+        return y if self.rank == 2 else y.squeeze(2)
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
-        return ops.maxpool_h2_bwd(dy.contiguous(), ctx.tape.pop(node.index))
+        if self.h2:
+            return ops.maxpool_h2_bwd(dy.contiguous(), ctx.tape.pop(node.index))
+        x4, shape = ctx.tape.pop(node.index)
+        dy = dy.contiguous()
+        pool, strides = self._pool2()
+        dx = ops.pool2d_bwd(self.mode, dy if self.rank == 2 else dy.unsqueeze(2), x4, shape, pool, strides, self.padding)
+        return dx if self.rank == 2 else dx.squeeze(2)
+
+
+class MaxPooling2D(_Pooling):
+    """keras.layers.MaxPooling2D.  bbhMahoGANy.py:444, :453, :462, ... (`maxpool = True`) place MaxPooling2D(pool_size=(2,1)) -- pairs of rows along
+    H; strides = pool_size, 'valid' -- which runs the two kernels of csrc/pool.hip; every other configuration runs csrc/pooling.hip.  The
+    gradient goes to the first maximum of a window in row-major order, as TensorFlow's."""
+    mode = 'max'
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding='valid', data_format=None, **kw):
+        _Pooling.__init__(self, pool_size, strides, padding, data_format, **kw)
+
+
+class AveragePooling2D(_Pooling):
+    """keras.layers.AveragePooling2D: under 'same' the divisor is the number of in-bounds cells of the window (TensorFlow excludes the padding)."""
+    mode = 'avg'
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding='valid', data_format=None, **kw):
+        _Pooling.__init__(self, pool_size, strides, padding, data_format, **kw)
+
+
+class MaxPooling1D(_Pooling):
+    """keras.layers.MaxPooling1D (the Conv1D -> MaxPooling1D(pool_size=2) blocks of the reference's tests/burstMahoGANy.py)."""
+    mode, rank = 'max', 1
+
+    def __init__(self, pool_size=2, strides=None, padding='valid', data_format=None, **kw):
+        _Pooling.__init__(self, pool_size, strides, padding, data_format, **kw)
+
+
+class AveragePooling1D(_Pooling):
+    mode, rank = 'avg', 1
+
+    def __init__(self, pool_size=2, strides=None, padding='valid', data_format=None, **kw):
+        _Pooling.__init__(self, pool_size, strides, padding, data_format, **kw)
+
+
+class _GlobalPooling(Layer):
+    """Keras 2.2.4 Global{Average,Max}Pooling{1D,2D}: (B, L, C) or (B, H, W, C) -> (B, C) over the (B, P, C) view.  The average's gradient is
+    dy / P; the maximum is K.max, whose gradient is dy / n_ties at every position equal to the maximum (tf.reduce_max), and the tape keeps x and
+    y for it in the training phase."""
+    mode, rank = None, 1
+
+    def __init__(self, data_format=None, **kw):
+        Layer.__init__(self, **kw)
+        if data_format not in (None, 'channels_last'):
+            raise NotImplementedError('%s(data_format=%r): channels_last only' % (type(self).__name__, data_format))
+
+    def compute_output_shape(self, input_shape):
+        if len(input_shape) != self.rank + 1:
+            raise ValueError('%s expects (batch, %s, channels) inputs, got %r' % (type(self).__name__, 'steps' if self.rank == 1 else 'rows, cols',
+                                                                                 (None,) + tuple(input_shape)))
+        return (input_shape[-1],)
+
+    def forward(self, ctx, node, x):
+        x3 = x.contiguous().reshape(x.shape[0], -1, x.shape[-1])
+        y = ops.global_pool_fwd(self.mode, x3)
+        if ctx.training:
+            ctx.tape[node.index] = (x3, y, tuple(x.shape)) if self.mode == 'max' else (None, None, tuple(x.shape))
+        return y
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        x3, y, shape = ctx.tape.pop(node.index)
+        return ops.global_pool_bwd(self.mode, dy.contiguous(), x3, y, (shape[0], int(np.prod(shape[1:-1])), shape[-1])).reshape(shape)
+
+
+class GlobalAveragePooling1D(_GlobalPooling):
+    """the tail of the sibling discriminator (2_model_version/*/subtract_model.py): GlobalAveragePooling1D() -> Dense(2, 'sigmoid')"""
+    mode, rank = 'avg', 1
+
+
+class GlobalAveragePooling2D(_GlobalPooling):
+    mode, rank = 'avg', 2
+
+
+class GlobalMaxPooling1D(_GlobalPooling):
+    mode, rank = 'max', 1
+
+
+class GlobalMaxPooling2D(_GlobalPooling):
+    mode, rank = 'max', 2
 
 
 class MyLayer(Layer):

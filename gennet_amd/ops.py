@@ -65,6 +65,22 @@ def conv_geometry(L, k, stride, padding):
     raise ValueError('padding %r' % (padding,))
 
 
+def pool_geometry(n, p, s, padding):
+    """(n_out, pad_before) of a pooling window p with stride s over n cells, Keras 2.2.4 on TensorFlow.  'valid': (n - p) // s + 1, the cells
+    behind the last full window are dropped (n < p: ValueError).  'same': ceil(n / s), the total pad max((n_out - 1) s + p - n, 0) with its
+    floor half in front, so the odd cell goes at the end (n < p included: the one window is clipped to the n cells).  Host only."""
+    n, p, s = int(n), int(p), int(s)
+    if n < 1 or p < 1 or s < 1:
+        raise ValueError('pooling %d cells with pool_size %d, strides %d' % (n, p, s))
+    if padding == 'same':
+        return same_pad(n, p, s)
+    if padding == 'valid':
+        if n < p:
+            raise ValueError("pool_size %d on %d cells with padding 'valid': no full window" % (p, n))
+        return (n - p) // s + 1, 0
+    raise ValueError('padding %r' % (padding,))
+
+
 # ---------------------------------------------------------------------------------------------- conv / dense
 def conv_needs_any(Cin, Cout):
     """True when the strict forward and weight gradient refuse this channel pair (gn_conv1d_needs_any): only conv1d_fwd / conv1d_wgrad with
@@ -261,6 +277,61 @@ def maxpool_h2_bwd(dy, x):
     R = x.numel() // max(B * H, 1)
     dx = torch.empty_like(x)
     _lib.call('gn_maxpool_h2_bwd', _p(dy), _p(x), _p(dx), B, H, R, _stream())
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------- pooling (csrc/pooling.hip)
+POOL_MODES = _lib.enum_members('GN_POOL_')                      # enum gn_pool: {'max': 0, 'avg': 1}
+
+
+def _pool_args(x_shape, pool, strides, padding):
+    """(B, H, W, C) and the geometry gn_pool2d_* take after it: ph, pw, sh, sw, pad_top, pad_left, Ho, Wo"""
+    B, H, W, C = (int(v) for v in x_shape)
+    (Ho, pt), (Wo, pl) = pool_geometry(H, pool[0], strides[0], padding), pool_geometry(W, pool[1], strides[1], padding)
+    return B, H, W, C, int(pool[0]), int(pool[1]), int(strides[0]), int(strides[1]), pt, pl, Ho, Wo
+
+
+def pool2d_fwd(mode, x, pool, strides, padding, out=None):
+    """x (B, H, W, C) -> (B, Ho, Wo, C): the maximum or the average ('max' | 'avg') over pool[0] x pool[1] windows, Keras 2.2.4 on TensorFlow."""
+    _chk(x, out)
+    B, H, W, C, ph, pw, sh, sw, pt, pl, Ho, Wo = _pool_args(x.shape, pool, strides, padding)
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(y.shape) == (B, Ho, Wo, C)
+    _lib.call('gn_pool2d_fwd', POOL_MODES[mode], _p(x), _p(y), B, H, W, C, ph, pw, sh, sw, pt, pl, Ho, Wo, _stream())
+    return y
+
+
+def pool2d_bwd(mode, dy, x, x_shape, pool, strides, padding, out=None):
+    """dx (x_shape) of pool2d_fwd; x may be None for 'avg' (the tape keeps only the shape)."""
+    _chk(dy, x, out)
+    B, H, W, C, ph, pw, sh, sw, pt, pl, Ho, Wo = _pool_args(x_shape, pool, strides, padding)
+    assert tuple(dy.shape) == (B, Ho, Wo, C) and (x is None or tuple(x.shape) == (B, H, W, C))
+    dx = torch.empty((B, H, W, C), dtype=torch.float32, device=dy.device) if out is None else out
+    _lib.call('gn_pool2d_bwd', POOL_MODES[mode], _p(dy), _p(x), _p(dx), B, H, W, C, ph, pw, sh, sw, pt, pl, Ho, Wo, _stream())
+    return dx
+
+
+def _global_pool_ws(B, P, C, device):
+    return workspace(_lib.size('gn_global_pool_workspace', B, P, C), device)           # 16-byte aligned, as every torch allocation is
+
+
+def global_pool_fwd(mode, x, out=None):
+    """x (B, P, C) -> (B, C): the mean or the maximum over P."""
+    _chk(x, out)
+    B, P, C = (int(v) for v in x.shape)
+    y = torch.empty((B, C), dtype=torch.float32, device=x.device) if out is None else out
+    ws = _global_pool_ws(B, P, C, x.device)
+    _lib.call('gn_global_pool_fwd', POOL_MODES[mode], _p(x), _p(y), _p(ws), ws.numel(), B, P, C, _stream())
+    return y
+
+
+def global_pool_bwd(mode, dy, x, y, x_shape, out=None):
+    """dx (x_shape = (B, P, C)); 'avg': dy / P, x and y may be None; 'max': dy / n_ties wherever x equals the maximum y."""
+    _chk(dy, x, y, out)
+    B, P, C = (int(v) for v in x_shape)
+    dx = torch.empty((B, P, C), dtype=torch.float32, device=dy.device) if out is None else out
+    ws = _global_pool_ws(B, P, C, dy.device)
+    _lib.call('gn_global_pool_bwd', POOL_MODES[mode], _p(dy), _p(x), _p(y), _p(dx), _p(ws), ws.numel(), B, P, C, _stream())
     return dx
 
 

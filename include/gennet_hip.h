@@ -208,6 +208,33 @@ int gn_upsample2_bwd(const float* dy, float* dx, int B, int L, int C, void* stre
  * the first row of the pair, as TensorFlow's max-pool gradient), zero elsewhere. */
 int gn_maxpool_h2_fwd(const float* x, float* y, int B, int H, int R, void* stream);
 int gn_maxpool_h2_bwd(const float* dy, const float* x, float* dx, int B, int H, int R, void* stream);
+/* ---- Keras 2.2.4 pooling layers (gennet_amd/csrc/pooling.hip): MaxPooling1D / AveragePooling1D of the reference's
+ * tests/burstMahoGANy.py, MaxPooling2D((2, 2)) of tests/ganymede.py, GlobalAveragePooling1D / 2D of 2_model_version/.../subtract_model.py ----
+ * Windowed: x (B, H, W, C) -> y (B, Ho, Wo, C), channels last; the 1-D layers are W = pw = sw = 1, pad_left = 0, Wo = 1.  Output (ho, wo) reads
+ * rows [ho*sh - pad_top, ho*sh - pad_top + ph) x columns [wo*sw - pad_left, wo*sw - pad_left + pw), clipped to the tensor; the caller computes
+ * Ho, Wo and the pads by TensorFlow's rule ('valid': (H - ph) / sh + 1, pads 0, the rows behind the last full window are dropped; 'same':
+ * ceil(H / sh), pad_top = max((Ho - 1) sh + ph - H, 0) / 2, the odd cell at the end).
+ *   GN_POOL_MAX: padded cells never win; a window of -inf gives -inf.  Backward: dy to the FIRST maximum of the window in row-major (h, w)
+ *                order (TensorFlow's max-pool gradient; gn_maxpool_h2_* is the (2,1)/(2,1) case, bit for bit), overlapping windows add.
+ *   GN_POOL_AVG: fp32 sum in row-major order / the number of IN-BOUNDS cells (TensorFlow excludes the padding).  Backward: dy / count summed
+ *                over the windows that cover the cell; x may be NULL.
+ * Both backward passes are gathers over dx (no atomics: identical bits on every run; cells no window covers are written as zero).
+ * Global: x (B, P, C) -> y (B, C), P = L or H*W.  GN_POOL_AVG: the fp64 sum over P in a fixed order, / P, rounded once; backward dy / P (x and
+ * y may be NULL).  GN_POOL_MAX: K.max = tf.reduce_max, whose gradient is dy / n_ties to EVERY position equal to the maximum -- not the
+ * first-maximum rule of the windowed layers.  ws: gn_global_pool_workspace(B, P, C) bytes, 16-byte aligned, serve both calls (the partials when
+ * P is split across blocks, and dy / n_ties per (b, c)).
+ * C % 4 == 0 on 16-byte aligned tensors runs with 16-byte loads and stores, anything else with scalar ones.  GN_EINVAL, nothing launched: a NULL
+ * pointer (except as above), C, H, W, P, pool or stride < 1, an unknown mode, a pad outside [0, pool), Ho / Wo < 1 or so large that a window
+ * holds no cell of the input.  B == 0 is GN_OK and launches nothing. */
+enum gn_pool { GN_POOL_MAX = 0, GN_POOL_AVG = 1 };
+int gn_pool2d_fwd(int mode, const float* x, float* y, int B, int H, int W, int C, int ph, int pw, int sh, int sw,
+                  int pad_top, int pad_left, int Ho, int Wo, void* stream);
+int gn_pool2d_bwd(int mode, const float* dy, const float* x, float* dx, int B, int H, int W, int C, int ph, int pw, int sh, int sw,
+                  int pad_top, int pad_left, int Ho, int Wo, void* stream);
+size_t gn_global_pool_workspace(int B, int P, int C);
+int gn_global_pool_fwd(int mode, const float* x, float* y, void* ws, size_t ws_bytes, int B, int P, int C, void* stream);
+int gn_global_pool_bwd(int mode, const float* dy, const float* x, const float* y, float* dx, void* ws, size_t ws_bytes, int B, int P, int C,
+                       void* stream);
 /* MyLayer (bbhMahoGANy.py:180-184): img[b,t,0] = x[b,t]; img[b,t,1] = event[t] - x[b,t];  adjoint dx = d0 - d1 */
 int gn_subtract_stack_fwd(const float* x, const float* event, float* img, int B, int n, void* stream);
 int gn_subtract_stack_bwd(const float* dimg, float* dx, int B, int n, void* stream);
