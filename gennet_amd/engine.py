@@ -452,14 +452,34 @@ class Layer(object):
 
     # -- functional API
     def __call__(self, x):
+        if isinstance(x, (list, tuple)):
+            # keras layers/merge.py: only a merge layer takes a list; its build / compute_output_shape receive the list of shapes
+            if not self.is_merge:
+                raise ValueError('%s (%s) takes a single tensor, not a list of %d: only the merge layers (Add, Subtract, Multiply, Average, Maximum, '
+                                 'Minimum, Concatenate) join tensors' % (self.name, type(self).__name__, len(x)))
+            if len(x) < 2:
+                raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s got %d)' % (self.name, len(x)))
+            shapes = [tuple(t.shape) for t in x]
+            if not self.built:
+                self.build(shapes)
+                self.built = True
+            return SymTensor(tuple(self.compute_output_shape(shapes)), self, tuple(x))
+        if self.is_merge:
+            raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s got a single tensor)' % self.name)
         self._ensure_built(x.shape)
         return SymTensor(self._shape_after(x.shape), self, (x,))
 
     # -- execution
+    is_merge = False         # joins several inbound tensors (layers._Merge, layers.Concatenate): forward takes the list, backward returns one
     fusable_act = False      # can take an activation epilogue
     fusable_drop = False     # can take a dropout epilogue
     act_spec = None          # (kind, param) if this layer IS an activation
     drop_rate = None         # rate if this layer IS a dropout
+
+    def writes_dy(self, node):
+        """Whether backward() overwrites the gradient it is handed (the in-place activation backward of the conv and dense layers).
+        Model._backward copies a gradient that another edge still holds before it hands it to such a layer."""
+        return False
 
     def forward(self, ctx, node, x):
         if not self._is_user_layer():
@@ -1019,31 +1039,62 @@ class Model(Layer):
         return [vals[i] for i in self.output_ids]
 
     def _backward(self, out_grads, ctx):
-        grads = {}
+        """Reverse sweep.  A layer's backward returns one tensor for its single inbound edge, or (merge layers) a list with one entry per inbound
+        edge, None where that edge gets no gradient; a merge layer is told which edges want one (need_dx is then a list of booleans: graph
+        inputs do not).  Fan-out gradients are summed into the tensor stored first, in place -- but only while no other edge holds the same
+        memory: Add hands one dy to all its inputs, Flatten / Reshape / absorbed nodes pass views on.  `held` counts, per storage, the pending
+        entries of `grads` that alias it.  An entry that shares its storage is not accumulated into: the first sum goes out of place
+        (ops.merge_fwd 'add', the traffic of the in-place axpy) and the result, owned, takes its place.  A layer that overwrites its dy
+        (Layer.writes_dy) gets a copy while another entry still holds that storage."""
+        grads, held = {}, {}
+
+        def key(t):                        # ops.ConvGrad1 (a deferred data gradient, never summed: Model._plan) stands for itself
+            return t.untyped_storage().data_ptr() if isinstance(t, torch.Tensor) else id(t)
+
+        def put(i, t):
+            g = grads.get(i)
+            if g is None:
+                grads[i] = t
+                held[key(t)] = held.get(key(t), 0) + 1
+            elif held[key(g)] > 1:
+                held[key(g)] -= 1
+                grads[i] = g = ops.merge_fwd('add', [g.contiguous(), t.contiguous().view(g.shape)])
+                held[key(g)] = held.get(key(g), 0) + 1
+            else:
+                ops.axpy(g, t, 1.0)
+
+        def take(i):
+            g = grads.pop(i, None)
+            if g is not None:
+                held[key(g)] -= 1
+                if not held[key(g)]:
+                    del held[key(g)]
+            return g
+
         for i, g in zip(self.output_ids, out_grads):
-            grads[i] = g
+            put(i, g)
         for n in reversed(self.nodes):
-            dy = grads.pop(n.index, None)
+            dy = take(n.index)
             if dy is None:
                 continue
             if n.absorbed:
-                dx = dy
+                dxs = [dy]
             else:
-                need_dx = any(i >= 0 for i in n.inbound)
+                wanted = [i >= 0 for i in n.inbound]
+                need_dx = any(wanted)
                 need_dw = ctx.wants_grad(n.layer)
                 if not need_dx and not need_dw:
                     continue
-                prev = ctx.epi.get(n.fuse_prev) if (n.fuse_prev >= 0 and need_dx) else None
-                dx = n.layer.backward(ctx, n, dy, need_dx, need_dw, prev) if prev is not None else n.layer.backward(ctx, n, dy, need_dx, need_dw)
-            if dx is None:
-                continue
-            for i in n.inbound:
-                if i < 0:
-                    continue
-                if i in grads:
-                    grads[i] = ops.axpy(grads[i], dx, 1.0)
+                if key(dy) in held and n.layer.writes_dy(n):
+                    dy = ops.scale(dy.contiguous(), 1.0)
+                if n.layer.is_merge:
+                    dxs = n.layer.backward(ctx, n, dy, wanted, need_dw)
                 else:
-                    grads[i] = dx
+                    prev = ctx.epi.get(n.fuse_prev) if (n.fuse_prev >= 0 and need_dx) else None
+                    dxs = [n.layer.backward(ctx, n, dy, need_dx, need_dw, prev) if prev is not None else n.layer.backward(ctx, n, dy, need_dx, need_dw)]
+            for i, dx in zip(n.inbound, dxs):
+                if i >= 0 and dx is not None:
+                    put(i, dx)
 
     # Model used as a layer inside another graph is expanded by _append, so forward/backward are never called on it.
 

@@ -8,6 +8,7 @@
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
+    from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, add, concatenate, ...                # all seven merge layers and functions
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -63,10 +64,12 @@ _pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'A
                  'GlobalMaxPooling1D', 'GlobalMaxPooling2D')
 _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU'), **_unused('39', 'ThresholdedReLU'))
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
+_merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate',
+               'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))
-for _d in (_core, _norm, _conv, _act, _noise):
+for _d in (_core, _norm, _conv, _act, _noise, _merge):
     _top.update((k, v) for k, v in _d.items() if v is _layers.__dict__.get(k))
 
 _TREE = {
@@ -81,6 +84,7 @@ _TREE = {
     'layers.advanced_activations': _act,
     'layers.noise': _noise,
     'layers.pooling': _pooling,
+    'layers.merge': _merge,
     'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
     'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }

@@ -219,6 +219,8 @@ def layer_config(layer):
         cfg.update(pool_size=list(layer.pool_size), padding=layer.padding, strides=list(layer.strides), data_format='channels_last')
     elif isinstance(layer, L._GlobalPooling):
         cfg.update(data_format='channels_last')
+    elif isinstance(layer, L.Concatenate):       # keras 2.2.4 layers/merge.py: the six element-wise layers write the base config only
+        cfg.update(axis=layer.axis)
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -324,6 +326,10 @@ def _layer_from_config(class_name, cfg, custom_objects):
                                       data_format=cfg.get('data_format'), **kw)
     if class_name in ('GlobalAveragePooling1D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'):
         return getattr(L, class_name)(data_format=cfg.get('data_format'), **kw)
+    if class_name in ('Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum'):
+        return getattr(L, class_name)(**kw)
+    if class_name == 'Concatenate':
+        return L.Concatenate(axis=cfg.get('axis', -1), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 
@@ -353,10 +359,8 @@ def model_from_config(config, custom_objects=None):
                     raise NotImplementedError('layer %s is called %d times; shared layers are not supported' % (e['name'], len(e['inbound_nodes'])))
                 elif all(ref[0] in tensors for ref in e['inbound_nodes'][0]):
                     ins = [tensors[ref[0]] for ref in e['inbound_nodes'][0]]
-                    if len(ins) != 1:
-                        raise NotImplementedError('layer %s has %d inputs; merge layers are not on the BBH path' % (e['name'], len(ins)))
                     layer = model_from_config(e, custom_objects) if e['class_name'] in ('Sequential', 'Model') else _layer_from_config(e['class_name'], e['config'], custom_objects)
-                    tensors[e['name']] = layer(ins[0])
+                    tensors[e['name']] = layer(ins[0] if len(ins) == 1 else ins)       # several inbound tensors: a merge layer (any other layer refuses the list)
                 else:
                     continue
                 pending.remove(e)

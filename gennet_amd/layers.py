@@ -54,6 +54,12 @@ def _conv_bwd_epilogue(dy, y, act, mask, rate, ctx=None, node=None):
     return dy
 
 
+def _epilogue_writes_dy(layer, node):
+    """Layer.writes_dy of the layers whose backward starts with _conv_bwd_epilogue: it overwrites dy unless the epilogue is linear and has no Dropout."""
+    a = node.fused_act or layer.activation
+    return a[0] != 'linear' or node.fused_drop is not None
+
+
 # A k-tap conv, 1 <= k <= 40, in its three directions.  More than 5 taps (`filtsize = 5 # 10 is best`, bbhMahoGANy.py:228) run as G = ceil(k/5) groups
 # of h = ceil(k/G) taps over the input with its shifted copies as further channel groups and the left padding materialised (csrc/tap_fold.hip): the
 # same <= 5-tap matrix-core kernels on 0 padding, the tap groups accumulating in their K loop; gradients come out folded and are unfolded.  Every
@@ -152,6 +158,9 @@ class Dense(Layer):
         if ctx.training and a[0] != 'linear':
             ctx.epi[node.index] = (y, a[0], a[1], None, 0.0)
         return y
+
+    def writes_dy(self, node):
+        return _epilogue_writes_dy(self, node)
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
         x, y, a = ctx.tape.pop(node.index)
@@ -262,6 +271,9 @@ class Conv1D(Layer):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
 
+    def writes_dy(self, node):
+        return _epilogue_writes_dy(self, node)
+
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
         t = ctx.tape.pop(node.index)
         run = t.run
@@ -326,6 +338,9 @@ class Conv2D(Layer):
         if ctx.training and (a[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], mask, rate)
         return y.reshape(B, Lout, 2, self.filters)
+
+    def writes_dy(self, node):
+        return _epilogue_writes_dy(self, node)
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
         t = ctx.tape.pop(node.index)
@@ -425,6 +440,9 @@ class Conv2DTranspose(Layer):
         if ctx.training and (a[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
+
+    def writes_dy(self, node):
+        return _epilogue_writes_dy(self, node)
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
         t = ctx.tape.pop(node.index)
@@ -1074,3 +1092,157 @@ class MyLayer(Layer):
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
         return ops.subtract_stack_bwd(dy.contiguous())
+
+
+# --------------------------------------------------------------------------------------------------------------
+# merge layers (keras layers/merge.py; csrc/merge.hip)
+# --------------------------------------------------------------------------------------------------------------
+def _merge_shapes(layer, input_shape, but_axis=None):
+    """The list of input shapes (no batch axis) of a merge layer, checked: 2 .. GN_MERGE_MAX_INPUTS tensors of one rank and, except along
+    `but_axis`, one shape.  Broadcasting between inputs is not provided."""
+    name = type(layer).__name__
+    if not isinstance(input_shape, (list, tuple)) or not input_shape or not isinstance(input_shape[0], (list, tuple)):
+        raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s)' % layer.name)
+    shapes = [tuple(s) for s in input_shape]
+    if len(shapes) < 2:
+        raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s got %d)' % (layer.name, len(shapes)))
+    if len(shapes) > ops.MERGE_MAX_INPUTS:
+        raise ValueError('%s on %d inputs: at most %d (GN_MERGE_MAX_INPUTS) are joined in one layer' % (name, len(shapes), ops.MERGE_MAX_INPUTS))
+    for s in shapes[1:]:
+        same = len(s) == len(shapes[0]) and all(a == b for d, (a, b) in enumerate(zip(s, shapes[0])) if d != but_axis)
+        if not same:
+            raise ValueError('%s: the inputs must have the same shape%s (no broadcasting between inputs), got %r and %r'
+                             % (name, '' if but_axis is None else ' except along the concatenation axis', (None,) + shapes[0], (None,) + s))
+    return shapes
+
+
+class _Merge(Layer):
+    """Keras 2.2.4 layers/merge.py _Merge on one pass of csrc/merge.hip: the inputs folded left to right in fp32, as keras' _merge_function loops.
+    Called on a list of 2 .. 8 tensors of one shape.  The backward returns one gradient per input (None where none is wanted): Add hands its dy to
+    every input and Average one scaled tensor to all of them -- Model._backward never writes into a tensor two edges hold.  The tape keeps the
+    inputs only where the gradient reads them (Multiply, Maximum, Minimum), in the training phase."""
+    is_merge = True
+    mode = None
+
+    def compute_output_shape(self, input_shape):
+        return _merge_shapes(self, input_shape)[0]
+
+    def forward(self, ctx, node, xs):
+        xs = [x.contiguous() for x in xs]
+        if ctx.training and self.mode in ('mul', 'max', 'min'):
+            ctx.tape[node.index] = xs
+        return ops.merge_fwd(self.mode, xs)
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        k = len(need_dx)
+        dy = dy.contiguous()
+        if self.mode in ('mul', 'max', 'min'):
+            xs = ctx.tape.pop(node.index)
+            return [ops.merge_bwd(self.mode, dy, xs, j) if w else None for j, w in enumerate(need_dx)]
+        if self.mode == 'add':
+            return [dy if w else None for w in need_dx]
+        if self.mode == 'sub':
+            return [dy if need_dx[0] else None, ops.scale(dy, -1.0) if need_dx[1] else None]
+        g = ops.scale(dy, float(np.float32(1.0) / np.float32(k))) if any(need_dx) else None          # 'avg'
+        return [g if w else None for w in need_dx]
+
+
+class Add(_Merge):
+    """keras.layers.Add: x0 + x1 + ... (a residual connection: Add()([block(h), h]))."""
+    mode = 'add'
+
+
+class Subtract(_Merge):
+    """keras.layers.Subtract: x0 - x1, exactly two inputs (bbhMahoGANy.py:1268: noise_signal - generated, on the host there)."""
+    mode = 'sub'
+
+    def compute_output_shape(self, input_shape):
+        if isinstance(input_shape, (list, tuple)) and len(input_shape) != 2:
+            raise ValueError('A `Subtract` layer should be called on exactly 2 inputs (%s got %d)' % (self.name, len(input_shape)))
+        return _Merge.compute_output_shape(self, input_shape)
+
+
+class Multiply(_Merge):
+    mode = 'mul'
+
+
+class Average(_Merge):
+    """keras.layers.Average: (x0 + x1 + ...) / k, the sum left to right and one division."""
+    mode = 'avg'
+
+
+class Maximum(_Merge):
+    """keras.layers.Maximum: K.maximum chained left to right; on a tie the gradient goes to the first input that attains the maximum."""
+    mode = 'max'
+
+
+class Minimum(_Merge):
+    mode = 'min'
+
+
+class Concatenate(Layer):
+    """keras.layers.Concatenate(axis=-1): the inputs side by side along `axis`, which counts the batch axis as in keras (axis 0 is refused).
+    One gather launch forward, one scatter launch backward (only into the inputs that want a gradient).
+    bbhMahoGANy.py:1268-1272 as layers: Concatenate(axis=-1)([g, Subtract()([event, g])])."""
+    is_merge = True
+
+    def __init__(self, axis=-1, **kw):
+        Layer.__init__(self, **kw)
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+            raise ValueError('Concatenate(axis=%r): an integer' % (axis,))
+        if axis == 0:
+            raise ValueError('Concatenate(axis=0): concatenating along the batch axis is refused')
+        self.axis = int(axis)
+
+    def _axis(self, rank):
+        """The axis of the (batch, ...) tensors of `rank` dimensions, 1 <= axis < rank."""
+        ax = self.axis + rank if self.axis < 0 else self.axis
+        if not 1 <= ax < rank:
+            raise ValueError('Concatenate(axis=%d) on inputs of %d dimensions (the batch axis included): the axis must be one of 1 .. %d or -1 .. %d; '
+                             'concatenating along the batch axis is refused' % (self.axis, rank, rank - 1, -(rank - 1)))
+        return ax
+
+    def compute_output_shape(self, input_shape):
+        if not isinstance(input_shape, (list, tuple)) or not input_shape or not isinstance(input_shape[0], (list, tuple)):
+            raise ValueError('A merge layer should be called on a list of at least 2 inputs (%s)' % self.name)
+        ax = self._axis(len(input_shape[0]) + 1) - 1
+        shapes = _merge_shapes(self, input_shape, ax)
+        return shapes[0][:ax] + (sum(s[ax] for s in shapes),) + shapes[0][ax + 1:]
+
+    def forward(self, ctx, node, xs):
+        xs = [x.contiguous() for x in xs]
+        if ctx.training:
+            ctx.tape[node.index] = [tuple(x.shape) for x in xs]
+        return ops.concat_fwd(xs, self._axis(xs[0].dim()))
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        shapes = ctx.tape.pop(node.index)
+        return ops.concat_bwd(dy.contiguous(), shapes, self._axis(len(shapes[0])), need_dx)
+
+
+def add(inputs, **kw):
+    return Add(**kw)(inputs)
+
+
+def subtract(inputs, **kw):
+    return Subtract(**kw)(inputs)
+
+
+def multiply(inputs, **kw):
+    return Multiply(**kw)(inputs)
+
+
+def average(inputs, **kw):
+    return Average(**kw)(inputs)
+
+
+def maximum(inputs, **kw):
+    return Maximum(**kw)(inputs)
+
+
+def minimum(inputs, **kw):
+    return Minimum(**kw)(inputs)
+
+
+def concatenate(inputs, axis=-1, **kw):
+    return Concatenate(axis=axis, **kw)(inputs)

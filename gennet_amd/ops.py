@@ -683,6 +683,95 @@ def axpy(y, x, a):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- merge layers (csrc/merge.hip)
+MERGE_MAX_INPUTS = _lib.CONSTS['GN_MERGE_MAX_INPUTS']
+MERGE_MODES = dict((k, v) for k, v in _lib.enum_members('GN_MERGE_').items() if k != 'max_inputs')     # enum gn_merge: {'add': 0, 'sub': 1, ...}
+
+
+def _ptr_table(ts):
+    """The host array of device pointers (None: NULL) the merge entry points read when they are called."""
+    return (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])
+
+
+def _merge_inputs(what, xs):
+    xs = list(xs)
+    if not 1 <= len(xs) <= MERGE_MAX_INPUTS:
+        raise ValueError('%s: %d inputs, 1 .. %d (GN_MERGE_MAX_INPUTS) are supported' % (what, len(xs), MERGE_MAX_INPUTS))
+    _chk(*xs)
+    if any(x.shape != xs[0].shape or x.dtype != torch.float32 for x in xs):
+        raise ValueError('%s: float32 inputs of one shape are expected, got %s' % (what, [tuple(x.shape) for x in xs]))
+    return xs
+
+
+def merge_fwd(mode, xs, out=None):
+    """x0 o x1 o ... left to right ('add' | 'sub' | 'mul' | 'avg' | 'max' | 'min'; 'avg': the sum / k), one pass over equal-shaped tensors."""
+    xs = _merge_inputs('merge_fwd', xs)
+    _chk(out)
+    y = torch.empty_like(xs[0]) if out is None else out
+    assert y.shape == xs[0].shape
+    _lib.call('gn_merge_fwd', MERGE_MODES[mode], _ptr_table(xs), len(xs), _p(y), y.numel(), _stream())
+    return y
+
+
+def merge_bwd(mode, dy, xs, which, out=None):
+    """The gradient of input `which` for 'mul' (dy times the other inputs) and 'max' / 'min' (dy where it is the first input at the extremum)."""
+    xs = _merge_inputs('merge_bwd', xs)
+    _chk(dy, out)
+    dx = torch.empty_like(dy) if out is None else out
+    assert dy.shape == xs[0].shape and dx.shape == dy.shape
+    _lib.call('gn_merge_bwd', MERGE_MODES[mode], _p(dy), _ptr_table(xs), len(xs), int(which), _p(dx), dy.numel(), _stream())
+    return dx
+
+
+def scale(x, a, out=None):
+    """a * x into a new tensor (x is not written: the gradient a merge layer receives is shared between its inputs)."""
+    _chk(x, out)
+    y = torch.empty_like(x) if out is None else out
+    _lib.call('gn_scale', _p(x), float(a), _p(y), x.numel(), _stream())
+    return y
+
+
+def _concat_views(shapes, axis):
+    """(outer, [w_i]) of tensors that differ along `axis` only: outer = the product of the dimensions in front, w_i = extent_i * those behind."""
+    outer = 1
+    for v in shapes[0][:axis]:
+        outer *= int(v)
+    widths = []
+    for s in shapes:
+        w = 1
+        for v in s[axis:]:
+            w *= int(v)
+        widths.append(w)
+    return outer, widths
+
+
+def concat_fwd(xs, axis, out=None):
+    """torch.cat(xs, axis) in one launch; axis >= 0 counts the batch axis."""
+    xs = list(xs)
+    _chk(*(xs + [out]))
+    shapes = [tuple(x.shape) for x in xs]
+    outer, widths = _concat_views(shapes, axis)
+    shape = shapes[0][:axis] + (sum(s[axis] for s in shapes),) + shapes[0][axis + 1:]
+    y = torch.empty(shape, dtype=torch.float32, device=xs[0].device) if out is None else out
+    assert tuple(y.shape) == shape and all(s[:axis] + s[axis + 1:] == shape[:axis] + shape[axis + 1:] for s in shapes)
+    _lib.call('gn_concat_fwd', _ptr_table(xs), (ctypes.c_int * len(xs))(*widths), len(xs), _p(y), outer, _stream())
+    return y
+
+
+def concat_bwd(dy, shapes, axis, wanted=None, outs=None):
+    """[dx_i or None] of concat_fwd in one launch: the slices of dy along `axis` for the inputs that are `wanted` (default: all)."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    wanted = [True] * len(shapes) if wanted is None else list(wanted)
+    _chk(dy)
+    outer, widths = _concat_views(shapes, axis)
+    assert dy.numel() == outer * sum(widths)
+    if outs is None:
+        outs = [torch.empty(s, dtype=torch.float32, device=dy.device) if w else None for s, w in zip(shapes, wanted)]
+    _chk(*outs)
+    _lib.call('gn_concat_bwd', _p(dy), _ptr_table(outs), (ctypes.c_int * len(shapes))(*widths), len(shapes), outer, _stream())
+    return outs
+
+
 # ---------------------------------------------------------------------------------------------- batch norm
 def bn_stats(x2d):
     """x2d: (rows, C) view.  Returns fp64 sums tensor (2*C,): [sum x | sum x^2]."""

@@ -267,6 +267,32 @@ int gn_gather_rows(const float* src, const int64_t* idx, float* out, int rows, i
 /* y[i] += a * x[i] */
 int gn_axpy(float* y, const float* x, float a, size_t n, void* stream);
 
+/* ---- Keras 2.2.4 merge layers (gennet_amd/csrc/merge.hip): Add, Subtract, Multiply, Average, Maximum, Minimum and
+ * Concatenate.  The reference forms `noise_signal - generated` and stacks it beside `generated` on the host at every iteration
+ * (bbhMahoGANy.py:1268-1272); with these the same is written in the model: Concatenate(axis=-1)([g, Subtract()([event, g])]).
+ * xs_host / dxs_host / widths_host are HOST arrays of n_inputs entries (1 .. GN_MERGE_MAX_INPUTS), read when the call is made: the device
+ * pointers travel to the kernel by value, nothing is copied and nothing synchronises, so a captured step replays.
+ * Element-wise, over n floats of any length and alignment (float4 body where y and every input are mutually 16-byte aligned, else an
+ * all-scalar pass); buffers must not overlap in part:
+ *   y = x0 o x1 o ... o x_{k-1} folded LEFT TO RIGHT in fp32, as keras' _merge_function loops.  GN_MERGE_AVG: that sum / (float)k, one
+ *   division.  GN_MERGE_SUB: k == 2.  GN_MERGE_MAX / MIN: b > a ? b : a (b < a), the earlier value stays on a tie (+-0 included).
+ *   gn_merge_bwd, the gradient of input `which`: GN_MERGE_MUL dx = dy * (product of x_j, j != which, left to right from the first such j;
+ *   x[which] is not read); GN_MERGE_MAX / MIN dx = dy where `which` is the FIRST input that attains the extremum, +0 elsewhere (TensorFlow's
+ *   _MaximumMinimumGrad under keras' chain of K.maximum).  The other modes have no kernel: Add dx = dy; Subtract, Average gn_scale by -1, 1 / k.
+ *   gn_scale: y = a * x, out of place (the gradient that arrives is shared between the inputs and is never written).
+ * Concatenate over the (outer, w_i) views, w_i = (extent of input i along the axis) * (product of the dimensions behind it):
+ *   gn_concat_fwd gathers y (outer, sum w_i) = [x_0 | x_1 | ...] in one launch; gn_concat_bwd scatters dy (outer, sum w_i) into the dx_i in
+ *   one launch, a NULL dx_i is skipped.  float4 units when every w_i % 4 == 0 and every pointer is 16-byte aligned, else floats.
+ * GN_EINVAL, nothing launched: a NULL pointer (except a dx_i), n_inputs outside 1 .. GN_MERGE_MAX_INPUTS (Subtract: != 2), an unknown mode or
+ * one without a backward kernel, `which` outside [0, n_inputs), a width < 1 or a total width >= 2^31.  n == 0 / outer == 0 is GN_OK. */
+#define GN_MERGE_MAX_INPUTS 8
+enum gn_merge { GN_MERGE_ADD = 0, GN_MERGE_SUB = 1, GN_MERGE_MUL = 2, GN_MERGE_AVG = 3, GN_MERGE_MAX = 4, GN_MERGE_MIN = 5 };
+int gn_merge_fwd(int mode, const float* const* xs_host, int n_inputs, float* y, size_t n, void* stream);
+int gn_merge_bwd(int mode, const float* dy, const float* const* xs_host, int n_inputs, int which, float* dx, size_t n, void* stream);
+int gn_scale(const float* x, float a, float* y, size_t n, void* stream);
+int gn_concat_fwd(const float* const* xs_host, const int* widths_host, int n_inputs, float* y, size_t outer, void* stream);
+int gn_concat_bwd(const float* dy, float* const* dxs_host, const int* widths_host, int n_inputs, size_t outer, void* stream);
+
 /* ---- BatchNormalization(momentum=0.99) (bbhMahoGANy.py:235 over 256*n_pix/2 features; :251,...,:284 over channels) ----
  * x is viewed as (rows, C).  Statistics are accumulated in fp64: sums[0:C] = sum x, sums[C:2C] = sum x^2.
  * Between gn_bn_stats and gn_bn_finalize a data-parallel caller all-reduces `sums` (SyncBN). */
