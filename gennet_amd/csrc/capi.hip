@@ -355,7 +355,7 @@ int gn_conv1d_fwd_stats(const float* x, const float* w, const float* bias, float
   GN_REQUIRE(x && w && y && sums && ws, "conv1d_fwd_stats: null pointer");
   GN_REQUIRE(B > 0 && L > 0 && Cin > 0 && Cout > 0 && Cout % 4 == 0 && k >= 1 && k <= 8 && stride >= 1 && Lout > 0, "conv1d_fwd_stats: bad shape");
   GN_REQUIRE(pad_left >= 0 && stride * (Lout - 1) + k - pad_left <= L + k, "conv1d_fwd_stats: Lout %d inconsistent with L %d k %d stride %d", Lout, L, k, stride);
-  GN_REQUIRE(ws_bytes >= gn_conv1d_fwd_stats_workspace(B, Lout, Cout), "conv1d_fwd_stats: workspace too small");
+  if (int rc = ws_check("conv1d_fwd_stats", gn_conv1d_fwd_stats_workspace(B, Lout, Cout), ws_bytes)) return rc;
   ConvArgs a = fwd_args(x, w, bias, y, B, L, Cin, Cout, k, stride, pad_left, Lout, GN_ACT_LINEAR, 0.f);
   int done = 0;
   a.stat_part = (double*)ws; a.stat_sums = sums; a.stat_done = &done;
@@ -492,7 +492,8 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* db, voi
   a.db = db;
   a.any_channels = any_channels;
   const WgradFamily f = select_wgrad(a);
-  int rc = ws_check("conv1d_wgrad", wgrad_ws_need(f, a), ws_bytes);
+  // what gn_conv1d_wgrad_workspace advertises for this call, to the byte: the family's slabs or the bias-gradient pass, whichever is larger
+  int rc = ws_check("conv1d_wgrad", std::max(wgrad_ws_need(f, a), bias_grad_ws((size_t)B * Lout, Cout)) + 256, ws_bytes);
   if (rc) return rc;
   switch (f) {
     case WGRAD_SMALL: {
@@ -554,14 +555,16 @@ int gn_dense_bwd(const float* x, const float* w, const float* dy, float* dx, flo
   hipStream_t s = (hipStream_t)stream;
   if (dense_any_shape(in, out)) {
     // dx = dy w^T, dw = x^T dy, db = column sums of dy (bias_grad: fixed order for out > 4)
-    GN_REQUIRE(ws && ws_bytes >= bias_grad_ws((size_t)B, out), "dense_bwd: workspace too small");
+    GN_REQUIRE(ws, "dense_bwd: null workspace");
+    if (int rc = ws_check("dense_bwd", gn_dense_bwd_workspace(B, in, out), ws_bytes)) return rc;
     int rc = dx ? dense_any_gemm(dy, w, nullptr, dx, B, in, out, (size_t)out, 1, 1, (size_t)out, GN_ACT_LINEAR, 0.f, s) : GN_OK;
     if (!rc) rc = dense_any_gemm(x, dy, nullptr, dw, in, out, B, 1, (size_t)in, (size_t)out, 1, GN_ACT_LINEAR, 0.f, s);
     if (!rc && db) rc = bias_grad(dy, db, (size_t)B, out, ws, ws_bytes, s);
     return rc;
   }
   if (out <= 4) return dense_small_bwd(x, w, dy, dx, dw, db, B, in, out, s);
-  GN_REQUIRE(ws && ws_bytes >= gn_dense_bwd_workspace(B, in, out), "dense_bwd: workspace too small");
+  GN_REQUIRE(ws, "dense_bwd: null workspace");
+  if (int rc = ws_check("dense_bwd", gn_dense_bwd_workspace(B, in, out), ws_bytes)) return rc;
   const size_t wt_bytes = (size_t)in * out * sizeof(float);
   float* wt = (float*)ws;
   void* ws2 = (char*)ws + wt_bytes;
