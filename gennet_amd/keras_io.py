@@ -183,7 +183,7 @@ def layer_config(layer):
         cfg.update(units=layer.units, activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
     elif isinstance(layer, L.Conv1D):
         cfg.update(filters=layer.filters, kernel_size=[layer.k], strides=[layer.stride], padding=layer.padding, data_format='channels_last',
-                   dilation_rate=[1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+                   dilation_rate=[layer.dilation], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
     elif isinstance(layer, L.Conv2DTranspose):
         # the keys (and values) keras 2.1.6 wrote for the reference's g_model.hdf5: no dilation_rate / output_padding
         cfg.update(filters=layer.filters, kernel_size=[1, layer.k], strides=[1, layer.stride], padding=layer.padding, data_format='channels_last',
@@ -284,7 +284,7 @@ def _layer_from_config(class_name, cfg, custom_objects):
     if class_name == 'Conv1D':
         init_ok(cfg.get('kernel_initializer'))
         return L.Conv1D(cfg['filters'], cfg['kernel_size'], strides=cfg.get('strides', 1), padding=cfg.get('padding', 'valid'), activation=cfg.get('activation'),
-                        use_bias=cfg.get('use_bias', True), **kw)
+                        use_bias=cfg.get('use_bias', True), dilation_rate=cfg.get('dilation_rate', 1), **kw)
     if class_name == 'Conv2D':
         init_ok(cfg.get('kernel_initializer'))
         return L.Conv2D(cfg['filters'], tuple(cfg['kernel_size']), strides=tuple(cfg.get('strides', (1, 1))), padding=cfg.get('padding', 'valid'),

@@ -102,15 +102,26 @@ class _ConvRun(object):
                              stride 1 its (L, 2 * filters) output is the layer's (2L, filters) output in memory)
       tap_folded             k > 5: launched as tap_groups(k)[1] taps on 0 padding over L + pl rows (_kconv_*), gradients unfolded with (L, pl)
       Cin_run, Cout_run      the launched channel pair; fwd_any: only the `anyc` kernels take it (ops.conv_needs_any); any_channels: it or the data
-                             gradient's swapped pair -- then no fusion that rests on a strict fused entry point is made"""
-    __slots__ = ('L', 'Cin', 'k', 'stride', 'pl', 'Lout', 'tap_folded', 'up_folded', 'Cin_run', 'Cout_run', 'fwd_any', 'any_channels')
+                             gradient's swapped pair -- then no fusion that rests on a strict fused entry point is made
+      phase                  None, or (d, pl, L, Lout) of a dilated or causal layer (Conv1D.phased): the conv above then is the layer's
+                             k taps on 0 padding over the d phase sequences of the padded input, a (B*d, M, Cin) batch -- L = M, pl = 0,
+                             Lout = (M - k) // stride + 1 -- between ops.dilate_split with these (d, pl) and ops.dilate_merge back to (L, Lout) rows"""
+    __slots__ = ('L', 'Cin', 'k', 'stride', 'pl', 'Lout', 'tap_folded', 'up_folded', 'Cin_run', 'Cout_run', 'fwd_any', 'any_channels', 'phase')
 
     def __init__(self, layer, Cin, up_folded, L=None):
-        self.L, self.Cin, self.up_folded, self.tap_folded = L, Cin, up_folded, layer.k > 5
+        self.L, self.Cin, self.up_folded, self.tap_folded, self.phase = L, Cin, up_folded, layer.k > 5, None
         self.k, self.stride = (3, 1) if up_folded else (layer.k, layer.stride)
         self.Cin_run, self.Cout_run = _launched_pair(layer.k, Cin, layer.filters, up_folded, layer.stride)
         self.fwd_any = ops.conv_needs_any(self.Cin_run, self.Cout_run)
         self.any_channels = self.fwd_any or ops.conv_needs_any(self.Cout_run, self.Cin_run)
+        if L is not None and layer.phased:
+            assert not up_folded
+            d = layer.dilation
+            Lout, pl = ops.conv_geometry(L, layer.k, layer.stride, layer.padding, d)
+            pr = (layer.k - 1) * d - pl if layer.padding == 'same' else 0
+            M = max(-(-(L + pl + pr) // d), layer.k)
+            self.phase, self.L, self.pl, self.Lout = (d, pl, L, Lout), M, 0, (M - layer.k) // layer.stride + 1
+            return
         self.Lout, self.pl = (None, None) if L is None else (L, 1) if up_folded else ops.conv_geometry(L, layer.k, layer.stride, layer.padding)
 
 
@@ -176,10 +187,25 @@ class Dense(Layer):
 
 
 class Conv1D(Layer):
-    """bbhMahoGANy.py:250-292, :362-394."""
+    """bbhMahoGANy.py:250-292, :362-394.
+
+    dilation_rate > 1 or padding='causal' (neither is in the reference): the layer is `phased` -- its own k-tap conv on 0 padding over
+    the d phase sequences of the zero-padded input (ops.dilate_split), the phases of the output put back in order (ops.dilate_merge).  Such an
+    instance runs on the same kernels as the undilated layer of its channel pair and takes part in none of the planner's cross-layer fusions: the
+    phase tensor has rows that are no output and is in another order than the tensors around it."""
     fusable_act = True
-    offers_act_bwd = True
-    can_absorb_prev_act_bwd = True
+
+    @property
+    def phased(self):
+        return self.dilation > 1 or self.padding == 'causal'
+
+    @property
+    def offers_act_bwd(self):
+        return not self.phased
+
+    @property
+    def can_absorb_prev_act_bwd(self):
+        return not self.phased
 
     @property
     def fusable_drop(self):
@@ -187,12 +213,15 @@ class Conv1D(Layer):
         runs on its own.  Asked before an UpSampling1D fold is decided, so for every 5-tap 'same' layer neither the unfolded nor the folded pair
         may need them, folded or not in the end: declining costs one pass, fusing wrongly an error.
         (For <= 4 filters that also turns the NotImplementedError of the fused Dropout into an unfused Dropout on such pairs, e.g. 8 -> 3.)"""
+        if self.phased:              # the mask would be in the layer's layout, the conv's epilogue in the phase layout
+            return False
         k = getattr(self, 'kernel', None)
         if k is None:
             return True
         return not any(_ConvRun(self, k.shape[1], up).any_channels for up in ((False, True) if self.can_fold_upsample() else (False,)))
 
-    def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
+    def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True,
+                 dilation_rate=1, **kw):
         Layer.__init__(self, **kw)
         _check_init(kernel_initializer)
         if not use_bias:
@@ -200,7 +229,17 @@ class Conv1D(Layer):
         self.filters = int(filters)
         self.k = int(kernel_size[0] if isinstance(kernel_size, (tuple, list)) else kernel_size)
         self.stride = int(strides[0] if isinstance(strides, (tuple, list)) else strides)
-        if padding not in ('same', 'valid'):
+        if isinstance(dilation_rate, (tuple, list)):
+            if len(dilation_rate) != 1:
+                raise ValueError('Conv1D(dilation_rate=%r): an integer or a tuple / list of 1 integer' % (dilation_rate,))
+            dilation_rate = dilation_rate[0]
+        self.dilation = int(dilation_rate)
+        if self.dilation < 1:
+            raise ValueError('Conv1D(dilation_rate=%r): must be >= 1' % (dilation_rate,))
+        if self.dilation > 1 and self.stride > 1:
+            raise ValueError('Conv1D(strides=%d, dilation_rate=%d): strides > 1 and dilation_rate > 1 exclude each other (as in Keras)'
+                             % (self.stride, self.dilation))
+        if padding not in ('same', 'valid', 'causal'):
             raise NotImplementedError('padding %r' % (padding,))
         self.padding = padding
         self.activation = _ACT_NAMES[activation]
@@ -212,6 +251,11 @@ class Conv1D(Layer):
                                       '(any stride >= 1 runs for <= 4 input channels)' % (self.stride, Cin))
         if not 1 <= self.k <= 40:
             raise NotImplementedError('Conv1D(kernel_size=%d): 1..40 taps (bbhMahoGANy.py:228 names 5 and 10)' % self.k)
+        if self.phased:
+            Lout = ops.conv_geometry(L, self.k, self.stride, self.padding, self.dilation)[0]
+            if Lout < 1:
+                raise ValueError('Conv1D(kernel_size=%d, dilation_rate=%d, padding=%r) on an input of shape %r: the output would have %d rows'
+                                 % (self.k, self.dilation, self.padding, tuple(input_shape), Lout))
         if self.stride > 2 and _ConvRun(self, Cin, False).fwd_any:      # (its data gradient's phases have unit input stride)
             raise NotImplementedError('Conv1D(%d filters, strides=%d) on %d input channels: strides above 2 run on the small-Cin kernels only, which '
                                       'need a multiple of 4 filters; the any-channel kernels implement strides 1 and 2'
@@ -220,19 +264,19 @@ class Conv1D(Layer):
         self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
 
     def compute_output_shape(self, input_shape):
-        return (ops.conv_geometry(input_shape[0], self.k, self.stride, self.padding)[0], self.filters)
+        return (ops.conv_geometry(input_shape[0], self.k, self.stride, self.padding, self.dilation)[0], self.filters)
 
     @property
     def can_fold_bn(self):
-        return self.activation[0] == 'linear' and self.filters % 4 == 0 and self.filters > 4
+        return self.activation[0] == 'linear' and self.filters % 4 == 0 and self.filters > 4 and not self.phased
 
     def can_defer_dgrad(self, Cin):
         """1 filter, stride 1: a BatchNormalization producer can form this layer's data gradient inside its own backward passes."""
-        return self.filters == 1 and self.stride == 1 and self.k <= 5 and Cin % 4 == 0 and not _NO_LAZYGRAD
+        return self.filters == 1 and self.stride == 1 and self.k <= 5 and Cin % 4 == 0 and not self.phased and not _NO_LAZYGRAD
 
     def can_fold_upsample(self):
         """UpSampling1D(2) in front folds into the weights (ops.conv1d_up2_fold): the engine's planner asks."""
-        return self.k == 5 and self.padding == 'same' and self.stride in (1, 2) and not _NO_UPFOLD
+        return self.k == 5 and self.padding == 'same' and self.stride in (1, 2) and not self.phased and not _NO_UPFOLD
 
     def _launch(self, run, x, w, b, launch):
         """`launch` (_kconv_fwd) on the operands of the conv that runs: tap-folded (k > 5), or the kernel with the upsample folded in (k == 5)"""
@@ -244,6 +288,17 @@ class Conv1D(Layer):
         a = node.fused_act or self.activation
         B = x.shape[0]
         run = _ConvRun(self, x.shape[2], node.fold_up is not None, x.shape[1])
+        if run.phase is not None:
+            # dilated or causal: the k taps on 0 padding over the phase sequences, bias and activation in that conv's epilogue (elementwise: they
+            # commute with the permutation), the output's phases merged back.  d == 1 (causal): the split only pads, the conv's output is y.
+            assert node.fused_drop is None and node.infer_bn is None and node.fold_up is None, 'a planner fusion on a dilated or causal Conv1D'
+            d, pl, _, Lout = run.phase
+            xs = ops.dilate_split(x, d, pl, run.L)
+            (ys, _, _), xs, w = self._launch(run, xs, self.kernel.data, self.bias.data, lambda *conv: _conv_fwd(
+                node, ctx, *conv, a, None, run.any_channels))
+            y = ops.dilate_merge(ys, B, d, 0, Lout) if d > 1 else ys
+            ctx.tape[node.index] = _ConvTape(xs, y, a, None, 0.0, w, run)
+            return y
         bn_node = None if run.any_channels else node.infer_bn
         if not ctx.training and bn_node is not None and run.Cin > 4:
             # inference phase: the following BatchNormalization (moving statistics) folds into the layer's own kernel, its activation into the
@@ -278,6 +333,17 @@ class Conv1D(Layer):
         t = ctx.tape.pop(node.index)
         run = t.run
         dy = _conv_bwd_epilogue(dy.contiguous().view(t.y.shape), t.y, t.act, t.mask, t.rate, ctx, node)
+        if run.phase is not None:
+            # the activation gradient above ran in the layer's own layout; the phases of dy (their surplus rows +0: they add nothing to dw and db)
+            # go through the undilated conv's two gradients, and the data gradient's phases merge back behind the pl padding rows
+            d, pl, L, _ = run.phase
+            dys = ops.dilate_split(dy, d, 0, run.Lout) if d > 1 else dy
+            if need_dw:
+                _kconv_wgrad(t.x, dys, run.k, run.stride, 0, self.kernel.grad, self.bias.grad, any_channels=run.any_channels, folded=True)
+            if not need_dx:
+                return None
+            dxs = _kconv_dgrad(dys, t.w, run.k, run.L, run.stride, 0, None, run.any_channels, folded=True)
+            return ops.dilate_merge(dxs, dy.shape[0], d, pl, L)
         if need_dw:         # t.x, t.w: as the forward launched them, folds included
             if run.up_folded:
                 dwf, dbf = _kconv_wgrad(t.x, dy, run.k, run.stride, run.pl, any_channels=run.any_channels)

@@ -57,11 +57,16 @@ def same_pad(L, k, s):
     return out, tot // 2
 
 
-def conv_geometry(L, k, stride, padding):
+def conv_geometry(L, k, stride, padding, dilation=1):
+    """(Lout, pad_left) of a k-tap conv with taps `dilation` rows apart: the geometry of its effective kernel (k - 1) * dilation + 1.
+    'causal' (Keras: pad (k - 1) * dilation rows on the left, then 'valid'): Lout = ceil(L / stride).  Host only."""
+    ke = (k - 1) * dilation + 1
     if padding == 'same':
-        return same_pad(L, k, stride)
+        return same_pad(L, ke, stride)
     if padding == 'valid':
-        return (L - k) // stride + 1, 0
+        return (L - ke) // stride + 1, 0
+    if padding == 'causal':
+        return -(-L // stride), ke - 1
     raise ValueError('padding %r' % (padding,))
 
 
@@ -770,6 +775,34 @@ def concat_bwd(dy, shapes, axis, wanted=None, outs=None):
     _chk(*outs)
     _lib.call('gn_concat_bwd', _p(dy), _ptr_table(outs), (ctypes.c_int * len(shapes))(*widths), len(shapes), outer, _stream())
     return outs
+
+
+# ---------------------------------------------------------------------------------------------- dilated / causal Conv1D (csrc/dilate.hip)
+def dilate_split(x, d, off, M, out=None):
+    """x (B, L, C) -> xs (B*d, M, C), the d phases of x behind `off` rows of padding: xs[b*d + p, m] = x[b, m*d + p - off] inside [0, L), +0
+    elsewhere; input rows beyond the M rows are dropped.  d = 1: a copy behind `off` zero rows."""
+    _chk(x, out)
+    B, L, C = (int(v) for v in x.shape)
+    d, off, M = int(d), int(off), int(M)
+    if d < 1 or M < 1:
+        raise ValueError('dilate_split: d %d, M %d must be >= 1' % (d, M))
+    xs = torch.empty((B * d, M, C), dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(xs.shape) == (B * d, M, C)
+    _lib.call('gn_dilate_split', _p(x), _p(xs), B, L, C, d, off, M, _stream())
+    return xs
+
+
+def dilate_merge(xs, B, d, off, L, out=None):
+    """xs (B*d, M, C) -> x (B, L, C), x[b, i] = xs[b*d + (i + off) % d, (i + off) // d]: the adjoint of dilate_split(x, d, off, M)."""
+    _chk(xs, out)
+    Bd, M, C = (int(v) for v in xs.shape)
+    B, d, off, L = int(B), int(d), int(off), int(L)
+    if B < 1 or d < 1 or L < 1 or Bd != B * d:
+        raise ValueError('dilate_merge: %d phase sequences are not B = %d times d = %d (L = %d)' % (Bd, B, d, L))
+    x = torch.empty((B, L, C), dtype=torch.float32, device=xs.device) if out is None else out
+    assert tuple(x.shape) == (B, L, C)
+    _lib.call('gn_dilate_merge', _p(xs), _p(x), B, L, C, d, off, M, _stream())
+    return x
 
 
 # ---------------------------------------------------------------------------------------------- batch norm

@@ -293,6 +293,18 @@ int gn_scale(const float* x, float a, float* y, size_t n, void* stream);
 int gn_concat_fwd(const float* const* xs_host, const int* widths_host, int n_inputs, float* y, size_t outer, void* stream);
 int gn_concat_bwd(const float* dy, float* const* dxs_host, const int* widths_host, int n_inputs, size_t outer, void* stream);
 
+/* ---- Conv1D(dilation_rate=d, padding='causal') (gennet_amd/csrc/dilate.hip): a stride-1 conv with dilation d is d
+ * independent undilated convs, one per phase (l mod d) of the zero-padded input.  Two memory-bound passes move a tensor into and out of
+ * that phase layout; the convs between them are the library's own, on a d times larger batch.
+ *   gn_dilate_split: x (B, L, C) -> xs (B*d, M, C).  With i = m*d + p - off: xs[b*d + p, m, :] = x[b, i, :] where 0 <= i < L, +0.0f
+ *     elsewhere.  Every element of xs is written; an input row that falls outside the M rows is dropped.  d = 1: a copy behind `off` zero rows.
+ *   gn_dilate_merge: xs (B*d, M, C) -> x (B, L, C), x[b, i, :] = xs[b*d + (i + off) % d, (i + off) / d, :]: the exact adjoint of the
+ *     split, a gather (no atomics), every element of x written once.
+ * float4 units when C % 4 == 0 and both base pointers are 16-byte aligned, else floats; element indices are size_t.
+ * GN_EINVAL, nothing launched: a NULL pointer, any of B, L, C, d, M < 1, off < 0; for the merge (L - 1 + off) / d >= M (a row outside xs). */
+int gn_dilate_split(const float* x, float* xs, int B, int L, int C, int d, int off, int M, void* stream);
+int gn_dilate_merge(const float* xs, float* x, int B, int L, int C, int d, int off, int M, void* stream);
+
 /* ---- BatchNormalization(momentum=0.99) (bbhMahoGANy.py:235 over 256*n_pix/2 features; :251,...,:284 over channels) ----
  * x is viewed as (rows, C).  Statistics are accumulated in fp64: sums[0:C] = sum x, sums[C:2C] = sum x^2.
  * Between gn_bn_stats and gn_bn_finalize a data-parallel caller all-reduces `sums` (SyncBN). */
