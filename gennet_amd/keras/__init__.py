@@ -5,7 +5,8 @@
     from gennet_amd.keras.layers.core import Activation, Flatten
     from gennet_amd.keras.layers.normalization import BatchNormalization
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
-    from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU
+    from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU, Softmax
+    from gennet_amd.keras.activations import softmax, relu, tanh, sigmoid, linear            # names for activation=
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, add, concatenate, ...                # all seven merge layers and functions
@@ -62,7 +63,7 @@ _conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'UpSampling1D
 _conv.update((n, _pooling_placeholder(n, '37-38')) for n in ('AveragePooling1D', 'MaxPooling1D'))
 _pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'AveragePooling2D', 'GlobalAveragePooling1D', 'GlobalAveragePooling2D',
                  'GlobalMaxPooling1D', 'GlobalMaxPooling2D')
-_act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU'), **_unused('39', 'ThresholdedReLU'))
+_act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU', 'Softmax'), **_unused('39', 'ThresholdedReLU'))
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate',
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate')
@@ -75,6 +76,7 @@ for _d in (_core, _norm, _conv, _act, _noise, _merge):
 _TREE = {
     'models': _pick(_engine, 'Model', 'Sequential', 'load_model', 'model_from_json'),
     'optimizers': dict(_pick(_engine, 'Adam', 'SGD', 'RMSprop', 'Adagrad', 'Adadelta', 'Adamax'), **_unused('43', 'Nadam')),
+    'activations': dict(_layers.ACTIVATIONS),
     'engine': {},
     'engine.topology': _pick(_engine, 'Layer'),
     'layers': _top,

@@ -165,7 +165,7 @@ def load_weights_from_group(g, layers):
 _GLOROT = {'class_name': 'VarianceScaling', 'config': {'scale': 1.0, 'mode': 'fan_avg', 'distribution': 'uniform', 'seed': None}}
 _ZEROS = {'class_name': 'Zeros', 'config': {}}
 _ONES = {'class_name': 'Ones', 'config': {}}
-_ACT_OF_SPEC = {'relu': 'relu', 'tanh': 'tanh', 'sigmoid': 'sigmoid', 'linear': 'linear'}
+_ACT_OF_SPEC = {'relu': 'relu', 'tanh': 'tanh', 'sigmoid': 'sigmoid', 'linear': 'linear', 'softmax': 'softmax'}
 
 
 def _kernel_part():
@@ -202,7 +202,9 @@ def layer_config(layer):
     elif isinstance(layer, L.ReLU):
         cfg.update(max_value=(layer.act_spec[1] if layer.act_spec[0] == 'relu_max' else None), negative_slope=0.0, threshold=0.0)
     elif isinstance(layer, L.Activation):
-        cfg.update(activation=_ACT_OF_SPEC[layer.act_spec[0]])
+        cfg.update(activation='softmax' if layer.softmax else _ACT_OF_SPEC[layer.act_spec[0]])
+    elif isinstance(layer, L.Softmax):
+        cfg.update(axis=layer.axis)
     elif isinstance(layer, L.Dropout):
         cfg.update(rate=layer.rate, noise_shape=None, seed=None)
     elif isinstance(layer, L.GaussianNoise):
@@ -306,6 +308,8 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.ReLU(max_value=cfg.get('max_value'), negative_slope=cfg.get('negative_slope', 0.0), threshold=cfg.get('threshold', 0.0), **kw)
     if class_name == 'Activation':
         return L.Activation(cfg['activation'], **kw)
+    if class_name == 'Softmax':
+        return L.Softmax(axis=cfg.get('axis', -1), **kw)
     if class_name == 'Dropout':
         return L.Dropout(cfg['rate'], **kw)
     if class_name == 'GaussianNoise':

@@ -20,6 +20,47 @@ _NO_UPFOLD = bool(_os.environ.get('GN_NO_UPFOLD'))        # A/B switch: material
 _NO_CONVSTATS = bool(_os.environ.get('GN_NO_CONVSTATS'))  # A/B switch: separate BatchNorm statistics pass instead of the conv epilogue
 
 _ACT_NAMES = {'relu': ('relu', 0.0), 'tanh': ('tanh', 0.0), 'sigmoid': ('sigmoid', 0.0), 'linear': ('linear', 0.0), None: ('linear', 0.0)}
+# softmax is no entry of ops.ACT: a reduction along an axis, not an epilogue.  A kernel layer with activation='softmax' keeps this spec, launches
+# its conv or dense kernel linear (_kernel_act) and runs ops.softmax_fwd over its channels behind it; the planner fuses nothing onto such a layer
+# (DESIGN 8k).  A callable of gennet_amd.keras.activations names itself.
+_SOFTMAX = ('softmax', 0.0)
+_LINEAR = ('linear', 0.0)
+
+
+def _act_spec(activation, what):
+    name = getattr(activation, '__name__', activation) if callable(activation) else activation
+    if name == 'softmax':
+        return _SOFTMAX
+    if name not in _ACT_NAMES:
+        raise NotImplementedError('%s(activation=%r): one of relu, tanh, sigmoid, linear, softmax' % (what, activation))
+    return _ACT_NAMES[name]
+
+
+def _activation_name(name):
+    def fn(x, *a, **k):
+        raise NotImplementedError('gennet_amd.keras.activations.%s is a name for activation=%r; applied to a tensor it has no HIP lowering: use the '
+                                  'layer (Activation(%r)%s)' % (name, name, name, ', Softmax(axis)' if name == 'softmax' else ''))
+    fn.__name__ = fn.__qualname__ = name
+    return fn
+
+
+ACTIVATIONS = dict((n, _activation_name(n)) for n in ('softmax', 'relu', 'tanh', 'sigmoid', 'linear'))      # gennet_amd.keras.activations
+
+
+def _kernel_act(a):
+    """the epilogue a conv or dense kernel is launched with for the layer activation `a`"""
+    return _LINEAR if a is _SOFTMAX else a
+
+
+def _is_softmax(layer):
+    return getattr(layer, 'activation', None) is _SOFTMAX
+
+
+def _channel_softmax(layer, y):
+    """softmax over the channels of a kernel layer's output, in place: the linear tensor is read by nothing else.  In memory the output of every
+    conv form (tap-folded, upsample-folded, width-2 Conv2D, Conv2DTranspose, the merged phases) is rows of layer.filters / layer.units floats."""
+    P = layer.units if hasattr(layer, 'units') else layer.filters
+    return ops.softmax_fwd(y, (y.numel() // P, P, 1), inplace=True)
 
 
 def _check_init(kernel_initializer):
@@ -32,6 +73,7 @@ def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any
     epilogue in the training phase; refused where the layer has none (drop_ok False: a Conv1D with <= 4 filters).  any_channels: the `anyc` kernels
     have no fused Dropout, and none arrives: Conv1D.fusable_drop declined it (Sequential and Model build a layer before they plan it)."""
     if node.fused_drop is not None:
+        assert act is not _SOFTMAX, 'a fused Dropout on a softmax layer'
         assert not any_channels, 'a fused Dropout on a channel pair of the any-channel kernels (plan the model after building it)'
         if not drop_ok:
             raise NotImplementedError('Dropout directly after a Conv1D with <= 4 filters')
@@ -39,12 +81,17 @@ def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any
             rate, drop_layer = node.fused_drop
             mask = drop_layer.make_mask(ctx, out_shape_for_mask)
             return ops.conv1d_fwd_dropout(x, w, b, mask, stride, pl, Lout, act[0], act[1], rate), mask, rate
+    act = _kernel_act(act)
     return ops.conv1d_fwd(x, w, b, stride, pl, Lout, act[0], act[1], any_channels=any_channels), None, 0.0
 
 
 def _conv_bwd_epilogue(dy, y, act, mask, rate, ctx=None, node=None):
     """gradient through [activation -> dropout] expressed through the layer output, in place, one pass -- unless the consumer's
     data-gradient kernel already applied it in its epilogue (engine backward fusion)."""
+    if act is _SOFTMAX:                # the softmax gradient first, from the stored output; what follows is the layer's backward with a linear epilogue
+        assert mask is None and node.index not in ctx.pre_applied
+        P = node.layer.units if hasattr(node.layer, 'units') else node.layer.filters
+        return ops.softmax_bwd(dy, y, (dy.numel() // P, P, 1), inplace=True)
     if ctx is not None and node.index in ctx.pre_applied:
         return dy
     if mask is not None:
@@ -139,7 +186,10 @@ _ConvTape = collections.namedtuple('_ConvTape', 'x y act mask rate w run pl in_s
 class Dense(Layer):
     """bbhMahoGANy.py:234 (100 -> 256*n_pix/2, MFMA GEMM), :377,:399,:494 (flatten -> 1 heads, streaming dot product)."""
     fusable_act = True
-    offers_act_bwd = True
+
+    @property
+    def offers_act_bwd(self):
+        return not _is_softmax(self)
 
     @property
     def can_absorb_prev_act_bwd(self):
@@ -152,7 +202,7 @@ class Dense(Layer):
         if not use_bias:
             raise NotImplementedError('Dense(use_bias=False)')
         self.units = int(units)
-        self.activation = _ACT_NAMES[activation]
+        self.activation = _act_spec(activation, 'Dense')
 
     def build(self, input_shape):
         assert len(input_shape) == 1, 'Dense expects (batch, features); Flatten first'
@@ -164,9 +214,12 @@ class Dense(Layer):
 
     def forward(self, ctx, node, x):
         a = node.fused_act or self.activation
-        y = ops.dense_fwd(x, self.kernel.data, self.bias.data, a[0], a[1])
+        ka = _kernel_act(a)
+        y = ops.dense_fwd(x, self.kernel.data, self.bias.data, ka[0], ka[1])
+        if a is _SOFTMAX:
+            y = _channel_softmax(self, y)
         ctx.tape[node.index] = (x, y, a)
-        if ctx.training and a[0] != 'linear':
+        if ctx.training and ka[0] != 'linear':
             ctx.epi[node.index] = (y, a[0], a[1], None, 0.0)
         return y
 
@@ -201,7 +254,7 @@ class Conv1D(Layer):
 
     @property
     def offers_act_bwd(self):
-        return not self.phased
+        return not self.phased and not _is_softmax(self)
 
     @property
     def can_absorb_prev_act_bwd(self):
@@ -214,6 +267,8 @@ class Conv1D(Layer):
         may need them, folded or not in the end: declining costs one pass, fusing wrongly an error.
         (For <= 4 filters that also turns the NotImplementedError of the fused Dropout into an unfused Dropout on such pairs, e.g. 8 -> 3.)"""
         if self.phased:              # the mask would be in the layer's layout, the conv's epilogue in the phase layout
+            return False
+        if _is_softmax(self):        # the conv's epilogue runs in front of the softmax pass, the Dropout behind it
             return False
         k = getattr(self, 'kernel', None)
         if k is None:
@@ -242,7 +297,7 @@ class Conv1D(Layer):
         if padding not in ('same', 'valid', 'causal'):
             raise NotImplementedError('padding %r' % (padding,))
         self.padding = padding
-        self.activation = _ACT_NAMES[activation]
+        self.activation = _act_spec(activation, 'Conv1D')
 
     def build(self, input_shape):
         L, Cin = input_shape
@@ -272,7 +327,8 @@ class Conv1D(Layer):
 
     def can_defer_dgrad(self, Cin):
         """1 filter, stride 1: a BatchNormalization producer can form this layer's data gradient inside its own backward passes."""
-        return self.filters == 1 and self.stride == 1 and self.k <= 5 and Cin % 4 == 0 and not self.phased and not _NO_LAZYGRAD
+        return (self.filters == 1 and self.stride == 1 and self.k <= 5 and Cin % 4 == 0 and not self.phased and not _is_softmax(self)
+                and not _NO_LAZYGRAD)
 
     def can_fold_upsample(self):
         """UpSampling1D(2) in front folds into the weights (ops.conv1d_up2_fold): the engine's planner asks."""
@@ -297,6 +353,8 @@ class Conv1D(Layer):
             (ys, _, _), xs, w = self._launch(run, xs, self.kernel.data, self.bias.data, lambda *conv: _conv_fwd(
                 node, ctx, *conv, a, None, run.any_channels))
             y = ops.dilate_merge(ys, B, d, 0, Lout) if d > 1 else ys
+            if a is _SOFTMAX:          # over the channels of the layer's own rows, the surplus rows of the phase tensor gone
+                y = _channel_softmax(self, y)
             ctx.tape[node.index] = _ConvTape(xs, y, a, None, 0.0, w, run)
             return y
         bn_node = None if run.any_channels else node.infer_bn
@@ -320,9 +378,11 @@ class Conv1D(Layer):
             return y
         (y, mask, rate), x, w = self._launch(run, x, self.kernel.data, self.bias.data, lambda *conv: _conv_fwd(
             node, ctx, *conv, a, (B, run.Lout, run.Cout_run), run.any_channels, self.filters > 4))
+        if a is _SOFTMAX:
+            y = _channel_softmax(self, y)
         ctx.tape[node.index] = _ConvTape(x, y, a, mask, rate, w, run)
         y = y.view(B, -1, self.filters)
-        if ctx.training and (a[0] != 'linear' or mask is not None):
+        if ctx.training and (_kernel_act(a)[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
 
@@ -368,9 +428,13 @@ class Conv2D(Layer):
     Executed as the exactly equivalent Conv1D over H with (w,c)-interleaved channels; the dead
     width taps kw in {0,4} receive zero gradient, as they do in the reference."""
     fusable_act = True
-    fusable_drop = True
-    offers_act_bwd = True
     can_absorb_prev_act_bwd = True
+
+    @property
+    def fusable_drop(self):
+        return not _is_softmax(self)
+
+    offers_act_bwd = fusable_drop
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
         Layer.__init__(self, **kw)
@@ -379,7 +443,7 @@ class Conv2D(Layer):
         self.kh, self.kw = (kernel_size, kernel_size) if isinstance(kernel_size, int) else tuple(kernel_size)
         self.sh, self.sw = (strides, strides) if isinstance(strides, int) else tuple(strides)
         self.padding = padding
-        self.activation = _ACT_NAMES[activation]
+        self.activation = _act_spec(activation, 'Conv2D')
         if self.kw != 5 or self.sw != 1 or padding != 'same' or not use_bias:
             raise NotImplementedError('Conv2D is implemented for the hot-path case only: kernel (kh,5), strides (sh,1), padding "same", width-2 input')
 
@@ -400,8 +464,10 @@ class Conv2D(Layer):
         wf, bf = ops.conv2d_w2_fold(self.kernel.data, self.bias.data)
         xf = x.reshape(B, H, 2 * Cin)
         y, mask, rate = _conv_fwd(node, ctx, xf, wf, bf, self.sh, pl, Lout, a, (B, Lout, 2, self.filters))
+        if a is _SOFTMAX:
+            y = _channel_softmax(self, y)
         ctx.tape[node.index] = _ConvTape(xf, y, a, mask, rate, wf, pl=pl, in_shape=x.shape)
-        if ctx.training and (a[0] != 'linear' or mask is not None):
+        if ctx.training and (_kernel_act(a)[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], mask, rate)
         return y.reshape(B, Lout, 2, self.filters)
 
@@ -441,7 +507,10 @@ class Conv2DTranspose(Layer):
     csrc/conv_transpose.hip; data gradient = the adjoint's forward; weight gradient = the adjoint's weight gradient with the operands swapped;
     more than 5 taps through the tap fold, as Conv1D does."""
     fusable_act = True
-    fusable_drop = True
+
+    @property
+    def fusable_drop(self):
+        return not _is_softmax(self)
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', output_padding=None, data_format=None, dilation_rate=(1, 1),
                  activation=None, use_bias=True, kernel_initializer='glorot_uniform', **kw):
@@ -463,7 +532,7 @@ class Conv2DTranspose(Layer):
         if self.k < self.stride:
             raise NotImplementedError('Conv2DTranspose(kernel (1, %d), strides (1, %d)): every stride phase needs a tap (kw >= s)' % (self.k, self.stride))
         self.padding = padding
-        self.activation = _ACT_NAMES[activation]
+        self.activation = _act_spec(activation, 'Conv2DTranspose')
 
     def build(self, input_shape):
         if len(input_shape) != 3:
@@ -491,6 +560,7 @@ class Conv2DTranspose(Layer):
         wadj = self.kernel.data.view(self.k, self.filters, Cin)         # the adjoint Conv1D's kernel (k, Cin=filters, Cout=Cin), no copy
         y = _kconv_dgrad(x3, wadj, self.k, Wout, self.stride, pl)
         mask, rate = None, 0.0
+        soft, a = a is _SOFTMAX, _kernel_act(a)            # softmax: the bias pass linear, then the softmax pass over the channels
         if ctx.training and node.fused_drop is not None and node.fused_drop[0] > 0.0:
             rate, drop_layer = node.fused_drop
             if ctx.dropout_masks.get(drop_layer.name) is None and ctx.row_map is None:
@@ -501,9 +571,11 @@ class Conv2DTranspose(Layer):
                 ops.bias_act_dropout(y, self.bias.data, a[0], a[1], mask, rate)
         else:
             ops.bias_act_dropout(y, self.bias.data, a[0], a[1])
+        if soft:
+            y, a = _channel_softmax(self, y), _SOFTMAX
         ctx.tape[node.index] = _ConvTape(x3, y, a, mask, rate, wadj, pl=pl, in_shape=x.shape)
         y = y.view(B, H, Wout, self.filters)
-        if ctx.training and (a[0] != 'linear' or mask is not None):
+        if ctx.training and (_kernel_act(a)[0] != 'linear' or mask is not None):
             ctx.epi[node.index] = (y, a[0], a[1], None if mask is None else mask.view(y.shape), rate)
         return y
 
@@ -708,19 +780,88 @@ class BatchNormalization(Layer):
         return dx.reshape(dy.shape)
 
 
-class Activation(Layer):
-    def __init__(self, activation, **kw):
+def _softmax_view(layer, axis, input_shape):
+    """(rows of `outer` per sample, P, inner) of a softmax over keras' `axis` (the batch axis counted, as BatchNormalization(axis=) counts it) of
+    inputs of `input_shape` (without the batch axis), with keras' refusals."""
+    n = len(input_shape) + 1
+    what = '%s (%s)' % (layer.name, type(layer).__name__)
+    if n == 1:
+        raise ValueError('%s: Cannot apply softmax to a tensor that is 1D' % what)
+    if axis == 0 or axis == -n:
+        raise ValueError('%s: softmax over axis %d is the batch axis: it would normalise across the samples of a batch, and under data parallelism '
+                         'across ranks; choose one of 1..%d or -1..-%d' % (what, axis, n - 1, n - 1))
+    if not (1 <= axis <= n - 1 or -(n - 1) <= axis <= -1):
+        raise ValueError('%s: softmax axis %d on inputs of shape %r: the axis must be one of 1..%d or -1..-%d'
+                         % (what, axis, (None,) + tuple(input_shape), n - 1, n - 1))
+    k = (axis if axis > 0 else axis + n) - 1
+    return (int(np.prod(input_shape[:k], dtype=np.int64)), int(input_shape[k]), int(np.prod(input_shape[k + 1:], dtype=np.int64)))
+
+
+class Softmax(Layer):
+    """keras.layers.Softmax(axis=-1) (layers/advanced_activations.py): exp(x - max) / sum exp(x - max) along `axis`, which counts the batch axis;
+    the batch axis itself is refused.  Two passes of csrc/softmax.hip on the (outer, P, inner) view, the gradient from the stored output.
+    No activation for the planner (act_spec stays None): nothing absorbs it and it absorbs nothing."""
+
+    def __init__(self, axis=-1, **kw):
         Layer.__init__(self, **kw)
-        if activation not in _ACT_NAMES:
-            raise NotImplementedError('Activation(%r)' % (activation,))
-        self.act_spec = _ACT_NAMES[activation]
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+            raise ValueError('%s (Softmax): axis=%r is not one integer' % (self.name, axis))
+        self.axis = int(axis)
+        self.view = None
+
+    def build(self, input_shape):
+        self.view = _softmax_view(self, self.axis, input_shape)
+
+    def compute_output_shape(self, input_shape):
+        _softmax_view(self, self.axis, input_shape)
+        return tuple(input_shape)
 
     def forward(self, ctx, node, x):
+        per, P, inner = self.view
+        view = (x.shape[0] * per, P, inner)
+        y = ops.softmax_fwd(x.contiguous(), view)
+        ctx.tape[node.index] = (y, view)
+        return y
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        y, view = ctx.tape.pop(node.index)
+        return ops.softmax_bwd(dy.contiguous(), y, view)
+
+
+class Activation(Layer):
+    """keras.layers.Activation.  Activation('softmax') is keras' softmax over the last axis: the Softmax layer's two passes under this layer's
+    name and config, and like it no activation for the planner."""
+
+    def __init__(self, activation, **kw):
+        Layer.__init__(self, **kw)
+        spec = _act_spec(activation, 'Activation')
+        self.softmax = spec is _SOFTMAX
+        self.act_spec = None if self.softmax else spec
+        self.view = None
+
+    softmax = False                                        # LeakyReLU, ReLU: element-wise
+
+    def build(self, input_shape):
+        if self.softmax:
+            self.view = _softmax_view(self, -1, input_shape)
+
+    def compute_output_shape(self, input_shape):
+        if self.softmax:
+            _softmax_view(self, -1, input_shape)
+        return tuple(input_shape)
+
+    forward_softmax, backward_softmax = Softmax.forward, Softmax.backward
+
+    def forward(self, ctx, node, x):
+        if self.softmax:
+            return self.forward_softmax(ctx, node, x)
         y = x if self.act_spec[0] == 'linear' else ops.act_fwd(x.contiguous(), self.act_spec[0], self.act_spec[1])
         ctx.tape[node.index] = y
         return y
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
+        if self.softmax:
+            return self.backward_softmax(ctx, node, dy, need_dx, need_dw)
         y = ctx.tape.pop(node.index)
         if self.act_spec[0] == 'linear':
             return dy

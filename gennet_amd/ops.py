@@ -460,6 +460,35 @@ def act_bwd(dy, y, act, act_param=0.0, inplace=False):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- softmax (csrc/softmax.hip)
+def _softmax_view(t, view):
+    outer, P, inner = (int(v) for v in view)
+    if outer < 1 or P < 1 or inner < 1 or outer * P * inner != t.numel():
+        raise ValueError('softmax: the (outer, P, inner) view %r does not cover a tensor of %d elements' % ((outer, P, inner), t.numel()))
+    if P * inner >= 1 << 31:
+        raise ValueError('softmax: P * inner = %d * %d does not fit the int parameters of the kernels (< 2^31)' % (P, inner))
+    return outer, P, inner
+
+
+def softmax_fwd(x, view, out=None, inplace=False):
+    """y = softmax of x along the middle axis of its (outer, P, inner) view (element (o, p, i) at (o*P + p)*inner + i); the shape stays x's."""
+    _chk(x, out)
+    outer, P, inner = _softmax_view(x, view)
+    y = x if inplace else torch.empty_like(x) if out is None else out
+    _lib.call('gn_softmax_fwd', _p(x), _p(y), outer, P, inner, _stream())
+    return y
+
+
+def softmax_bwd(dy, y, view, out=None, inplace=False):
+    """dx = y * (dy - sum_p dy * y) from the stored output y, on the same view"""
+    _chk(dy, y, out)
+    outer, P, inner = _softmax_view(dy, view)
+    assert y.numel() == dy.numel()
+    dx = dy if inplace else torch.empty_like(dy) if out is None else out
+    _lib.call('gn_softmax_bwd', _p(dy), _p(y), _p(dx), outer, P, inner, _stream())
+    return dx
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

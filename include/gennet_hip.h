@@ -387,6 +387,16 @@ int gn_bn_axis_bwd_apply(const float* dy, const float* x, const float* gamma, co
                          const double* dsums_global, double count, const double* dsums_local, float* dx, float* dgamma, float* dbeta,
                          void* ws, size_t ws_bytes, size_t outer, int P, int inner, void* stream);
 
+/* ---- softmax along one axis (csrc/softmax.hip; keras activations.softmax, layers.Softmax(axis)) on the same (outer, P, inner)
+ * view: y = exp(x - max_p x) / sum_p exp(x - max_p x); dx = y * (dy - sum_p dy * y) from the stored output y.  inner == 1 is the channel
+ * softmax of a dense or conv output.  No workspace.  fp32 reductions in a fixed order, no atomics: repeated runs give identical bits.
+ * Bytes per element: forward 8 and backward 12 while a row fits the lanes that own it (inner == 1: P <= 4096; inner >= 16: P <= 16, float4
+ * columns 8; inner < 16: P <= 16 * (64 / inner)), beyond that 12 and 20 (running maximum, sum rescaled once per tile, second read).
+ * y may alias x, dx may alias dy.  Inputs are finite; a row holding +-3e38 gives exact 0 and 1.
+ * GN_EINVAL, nothing launched: a NULL pointer, outer / P / inner < 1, P * inner >= 2^31, outer * P * inner >= 2^62. */
+int gn_softmax_fwd(const float* x, float* y, size_t outer, int P, int inner, void* stream);
+int gn_softmax_bwd(const float* dy, const float* y, float* dx, size_t outer, int P, int inner, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
