@@ -68,6 +68,25 @@ __device__ __forceinline__ void epi_store(const ConvArgs& a, const EpiSrd& s, fl
   }
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), s.y, voff * 4, soff * 4, GN_STORE_AUX);
 }
+// The arithmetic of epi_store alone, for the epilogue that loads and stores four elements at once (tile16_wide_epilogue): k = the element's keep byte
+// (MODE 1, 3), gv = the producer's output there (MODE >= 2).  The same operations in the same order, so the same bits; the two stay in step.  (epi_store
+// keeps its own copy: built on this function the direct kernels' ISA came out different, and they are not to change.)
+template <int ACT, int MODE, int GACT>
+__device__ __forceinline__ float epi_value(const ConvArgs& a, const EpiSrd& s, float v, unsigned k, float gv) {
+  if (ACT == GN_ACT_RELU) v = fmaxf(v, 0.f);
+  else if (ACT == GN_ACT_LEAKY) v = v > 0.f ? v : a.act_param * v;
+  else if (ACT == GN_ACT_TANH) v = gn_tanhf(v);
+  else if (ACT != GN_ACT_LINEAR) v = act_apply(v, a.act, a.act_param);
+  if (MODE == 1) v = k ? v * a.keep_scale : 0.f;
+  if (MODE == 3) {
+    const float y0 = gv * s.ginv;
+    const float dg = GACT == GN_ACT_LEAKY ? (y0 > 0.f ? 1.f : a.gparam) : act_grad_from_y(y0, a.gact, a.gparam);
+    v = k ? v * a.gscale * dg : 0.f;
+  } else if (MODE == 2) {
+    v *= GACT == GN_ACT_RELU ? (gv > 0.f ? 1.f : 0.f) : act_grad_from_y(gv, a.gact, a.gparam);
+  }
+  return v;
+}
 
 template <int ACT, int MODE, int GACT, int WN, int WMT = 2>
 __device__ __forceinline__ void pipe_epilogue(const ConvArgs& a, const f32x16 (&acc)[WMT][WN], int b, int m_base, int n_base, int i32, int h, int out_off) {
@@ -128,6 +147,89 @@ __device__ __forceinline__ void tile16_epilogue_dispatch(const ConvArgs& a, cons
     else GN_EPI(-1, 3, -1);
   }
 #undef GN_EPI
+}
+
+// The 16-byte form of tile16_epilogue for TWO such tiles (the output phases off0 and off1 of the same 16 rows), through LDS: in the accumulator
+// layout one buffer instruction covers 4 rows x 64 bytes; turned through a wave-private LDS region (2 x 16 rows x 64 columns, 8 KiB: `wreg`, free
+// once the block is past the K loop's last barrier) one covers 4 rows x 256 bytes -- 16 lanes a row -- so a wave issues 8 stores (8 gy loads, 8 mask
+// loads of four keep bytes) instead of 32.  A row is 256 bytes of LDS: the ds_write_b32 of the accumulator layout are 2-way (free on a 4-cycle
+// instruction), the ds_read_b128 lane groups (MI355X: 0-3, 12-15, 20-27 | ...) each cover the 64 banks once.  Bias is added on the way in and
+// epi_value runs on the four elements, so every element is computed by the operations of epi_store in their order: the same bits at the same
+// addresses.  Needs the bases of y and gy 16-byte aligned and the mask's 4-byte aligned (Cout % 64 == 0 keeps every row so): the launch checks.
+typedef unsigned u32x4e __attribute__((ext_vector_type(4)));
+constexpr int kWideEpiFloats = 2 * 16 * 64;      // LDS floats of one wave's region
+template <int ACT, int MODE, int GACT>
+__device__ __forceinline__ void tile16_wide_epilogue(const ConvArgs& a, const f32x4e (&o0)[4], const f32x4e (&o1)[4], float* wreg, int b, int m_base, int n_base,
+                                                     int lane, int off0, int off1) {
+  const EpiSrd srd = epi_srd<MODE>(a, b);
+  const int rowstride = a.t.out_stride * a.Cout;
+  const int n16 = lane & 15, kq = lane >> 4;
+  float* wr = wreg + (4 * kq) * 64 + n16;
+  float bias[4] = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias) {                                           // the four loads in flight together
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) bias[ct] = a.bias[n_base + ct * 16 + n16];
+  }
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      wr[r * 64 + ct * 16] = o0[ct][r] + bias[ct];
+      wr[1024 + r * 64 + ct * 16] = o1[ct][r] + bias[ct];
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the LDS serves a wave's operations in order: this keeps the compiler from moving the reads up)
+  const int c4 = 4 * n16;                                  // this lane's four columns of row 4 g + kq
+  const float* rd = wreg + kq * 64 + c4;
+  const int voff = rowstride * kq + n_base + c4;
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      f32x4e v = *reinterpret_cast<const f32x4e*>(rd + ph * 1024 + g * 256);
+      const int soff = rowstride * (m_base + 4 * g) + (ph ? off1 : off0) * a.Cout;      // wave-uniform
+      unsigned k4 = 0;
+      u32x4e g4 = {0u, 0u, 0u, 0u};
+      if (MODE == 1 || MODE == 3) k4 = __builtin_amdgcn_raw_buffer_load_b32(srd.m, voff, soff, 0);
+      if (MODE >= 2) g4 = __builtin_amdgcn_raw_buffer_load_b128(srd.g, voff * 4, soff * 4, 0);
+      u32x4e o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float ve = v[e];                             // (scalars first: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index)
+        const unsigned ge = g4[e];
+        o[e] = __builtin_bit_cast(unsigned, epi_value<ACT, MODE, GACT>(a, srd, ve, (k4 >> (8 * e)) & 0xffu, __builtin_bit_cast(float, ge)));
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(o, srd.y, voff * 4, soff * 4, GN_STORE_AUX);
+    }
+  }
+}
+__device__ __forceinline__ void tile16_wide_epilogue_dispatch(const ConvArgs& a, const f32x4e (&o0)[4], const f32x4e (&o1)[4], float* wreg, int b, int m_base,
+                                                              int n_base, int lane, int off0, int off1, int mode) {
+#define GN_EPI(A_, M_, G_) tile16_wide_epilogue<A_, M_, G_>(a, o0, o1, wreg, b, m_base, n_base, lane, off0, off1)
+  if (mode == 0) {
+    switch (a.act) {
+      case GN_ACT_LINEAR: GN_EPI(GN_ACT_LINEAR, 0, -1); break;
+      case GN_ACT_RELU: GN_EPI(GN_ACT_RELU, 0, -1); break;
+      case GN_ACT_LEAKY: GN_EPI(GN_ACT_LEAKY, 0, -1); break;
+      case GN_ACT_TANH: GN_EPI(GN_ACT_TANH, 0, -1); break;
+      default: GN_EPI(-1, 0, -1); break;
+    }
+  } else if (mode == 1) {
+    if (a.act == GN_ACT_LEAKY) GN_EPI(GN_ACT_LEAKY, 1, -1);
+    else GN_EPI(-1, 1, -1);
+  } else if (mode == 2) {
+    if (a.act == GN_ACT_LINEAR && a.gact == GN_ACT_RELU) GN_EPI(GN_ACT_LINEAR, 2, GN_ACT_RELU);
+    else GN_EPI(-1, 2, -1);
+  } else {
+    if (a.act == GN_ACT_LINEAR && a.gact == GN_ACT_LEAKY) GN_EPI(GN_ACT_LINEAR, 3, GN_ACT_LEAKY);
+    else GN_EPI(-1, 3, -1);
+  }
+#undef GN_EPI
+}
+// host side of the above: the base addresses a launch's 16-byte epilogue needs
+static inline bool wide_epilogue_aligned(const ConvArgs& a) {
+  const uintptr_t mk = (uintptr_t)(a.gy ? a.gmask : a.mask);
+  return (uintptr_t)a.y % 16 == 0 && (uintptr_t)a.gy % 16 == 0 && mk % 4 == 0;
 }
 
 // uniform dispatch, decided once per wave; every case is straight-line code.  Specialised: the forms the three networks run (forward

@@ -67,21 +67,22 @@ __global__ void wino_u_kernel(const float* __restrict__ w, float* __restrict__ U
 // (wino_slot, wino_slot_rb: wino_common.h)
 // ---------------------------------------------------------------------------------------------
 // ... and the raw fragments of the next chunk (slot 0); this point's U values were read across the barrier: the wait retires them
-template <int O, int OP1>
+template <int O, int OP1, int OA = 0>
 __device__ __forceinline__ void wino_slot_rba(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b, f32x2 (&d)[6], unsigned addr_a) {
   asm volatile(
       "ds_read_b128 %1, %11 offset:%13\n\t"
       "ds_read_b128 %2, %11 offset:%14\n\t"
-      "ds_read_b64 %3, %12\n\t"
+      "ds_read_b64 %3, %12 offset:%18\n\t"
       "ds_read_b64 %4, %12 offset:%15\n\t"
-      "ds_read_b64 %5, %12 offset:32\n\t"
+      "ds_read_b64 %5, %12 offset:%19\n\t"
       "ds_read_b64 %6, %12 offset:%16\n\t"
-      "ds_read_b64 %7, %12 offset:64\n\t"
+      "ds_read_b64 %7, %12 offset:%20\n\t"
       "ds_read_b64 %8, %12 offset:%17\n\t"
       "s_waitcnt lgkmcnt(8)\n\t"
       "v_mfma_f32_16x16x4_f32 %0, %9, %10, %0"
       : "+v"(c), "=&v"(nb0), "=&v"(nb1), "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5])
-      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(OP1), "i"(OP1 + 32), "i"(OP1 + 64)
+      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(OA + OP1), "i"(OA + OP1 + 32), "i"(OA + OP1 + 64), "i"(OA), "i"(OA + 32),
+        "i"(OA + 64)
       : "memory");
 }
 // ... slot 8: its wait also retires the raw fragments (issued before the reads this slot adds); they are operands so that their readers depend on it
@@ -97,7 +98,9 @@ __device__ __forceinline__ void wino_slot_rbw(f32x4& c, float a, float b, f32x4&
       : "memory");
 }
 
-template <int RPER, int ABL = 0>
+// OB, OBN, OA: byte offsets of this chunk's stage (U values), of the next chunk's stage (its point-0 U values; its raw fragments) inside the asm's
+// immediates -- the unrolled chunks of the main loop pass the stage-0 addresses and their stage here, the tail loop the stage's addresses and 0
+template <int RPER, int ABL = 0, int OB = 0, int OBN = 0, int OA = 0>
 struct WinoChunk {
   template <int NPIECES, int I = 0, class D>
   static __device__ __forceinline__ void run(f32x4 (&acc)[6][4], const f32x2 (&v)[6], f32x2 (&vn)[6], f32x2 (&d)[6], WinoT& t, f32x4 (&B)[2][2], unsigned addr_b,
@@ -109,10 +112,10 @@ struct WinoChunk {
       const float bv = bc[CT >> 1][2 * (CT & 1) + S];
       const float av = v[P][S];
       if constexpr ((ABL & 8) != 0) wino_slot(acc[P][CT], av, bv);
-      else if constexpr (I == 0) wino_slot_rba<2048, RPER * 32>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
-      else if constexpr (I == 8) wino_slot_rbw<2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
-      else if constexpr (I == 40) wino_slot_rb<0, 2>(acc[5][0], av, bv, bn[0], bn[1], addr_b_next);
-      else if constexpr (I % 8 == 0) wino_slot_rb<(P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
+      else if constexpr (I == 0) wino_slot_rba<OB + 2048, RPER * 32, OA>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
+      else if constexpr (I == 8) wino_slot_rbw<OB + 2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
+      else if constexpr (I == 40) wino_slot_rb<OBN, 2>(acc[5][0], av, bv, bn[0], bn[1], addr_b_next);
+      else if constexpr (I % 8 == 0) wino_slot_rb<OB + (P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
       else wino_slot(acc[P][CT], av, bv);
       if constexpr ((I & 1) && (I >> 1) < NPIECES) dma(std::integral_constant<int, (I >> 1)>{});
       if constexpr (!(ABL & 2)) {
@@ -132,7 +135,7 @@ struct WinoChunk {
 // loop, bit 1 = no transform, bit 2 = no barrier, bit 3 = no LDS reads in the loop
 template <int WAVES_M, int ABL = 0>
 __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino_kernel(ConvArgs a, const float* __restrict__ U, int off0, int m_tiles, int n_tiles,
-                                                                                        int patch) {
+                                                                                        int patch, int wide) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int KC = 8, NP = 6;
   constexpr int TT = WAVES_M * 16;                 // tiles (output row pairs) per block
@@ -143,6 +146,8 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
   constexpr int UT = NP * KC * TN;                 // 3072 floats
   constexpr int BUF = SLAB + UT;
   constexpr int STAGE_BYTES = BUF * 4;
+  constexpr int RED = WAVES_M * kWideEpiFloats;    // floats: the epilogue's wave regions lie in front of the statistics' partial sums
+  static_assert(RED * 4 + WAVES_M * TN * 16 <= 3 * STAGE_BYTES, "epilogue regions");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -233,9 +238,30 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
     Bq[0][0] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0));
     Bq[0][1] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0) + 1024);
   }
-  int st = 0;
+  int st = 0, ch = 0;
   in_loop = true;
-  for (int ch = 0; ch < n_chunks; ch += 2) {
+  // Six chunks at a time -- the three stages x the two V buffers -- with every stage address an immediate on the chunk-invariant stage-0 address: no
+  // vector add of a stage offset sits between the MFMAs (a lone vector instruction there costs 14.5-16 cycles: scripts/valu_rate.hip).  Same chunks in
+  // the same order into the same accumulators as the loop below, which runs what is left (n_chunks % 6; stage 0 and V0 again after every six).
+  static_assert(2 * STAGE_BYTES + 6 * 2048 + RPER * 32 + 64 < 65536, "stage offsets as ds_read immediates");
+  auto chunk_of_six = [&](auto jc) {
+    constexpr int J = decltype(jc)::value, S0 = J % 3, S1 = (J + 1) % 3, S2 = (J + 2) % 3;
+    c_next = min(ch + J + 2, n_chunks - 1);
+    st_next = S2;
+    using Chunk = WinoChunk<RPER, ABL, S0 * STAGE_BYTES, S1 * STAGE_BYTES, S1 * STAGE_BYTES>;
+    if constexpr (J % 2 == 0) Chunk::template run<NPIECES>(acc, V0, V1, d, tt, Bq, base_b, base_b, base_a, k15, km15, dma_piece);
+    else Chunk::template run<NPIECES>(acc, V1, V0, d, tt, Bq, base_b, base_b, base_a, k15, km15, dma_piece);
+    if constexpr (!(ABL & 4)) __syncthreads();
+  };
+  for (; ch + 6 <= n_chunks; ch += 6) {
+    chunk_of_six(std::integral_constant<int, 0>{});
+    chunk_of_six(std::integral_constant<int, 1>{});
+    chunk_of_six(std::integral_constant<int, 2>{});
+    chunk_of_six(std::integral_constant<int, 3>{});
+    chunk_of_six(std::integral_constant<int, 4>{});
+    chunk_of_six(std::integral_constant<int, 5>{});
+  }
+  for (; ch < n_chunks; ch += 2) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       if (half == 1 && ch + 1 >= n_chunks) break;
@@ -250,8 +276,9 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
       st = st1;
     }
   }
-  // MFMA results written inside asm: the compiler inserts no wait states for its own readers of acc
-  asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[5][0]), "+v"(acc[5][1]), "+v"(acc[5][2]), "+v"(acc[5][3]));
+  // MFMA results written inside asm: the compiler inserts no wait states for its own readers of acc; nor does it count the last chunk's prefetch reads
+  // (their values are dead, their registers are not: the wait retires them before the epilogue reuses either)
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 7" : "+v"(acc[5][0]), "+v"(acc[5][1]), "+v"(acc[5][2]), "+v"(acc[5][3]));
 
   // AT: even rows = p0 + p1 + p2 + p3 + p4, odd rows = p1 - p2 + p3 / 2 - 2 p4 + p5
   f32x4 out[2][4];
@@ -266,11 +293,17 @@ __global__ __launch_bounds__(64 * WAVES_M, (WAVES_M > 4 ? 1 : 2)) void conv_wino
   const int mode = a.gy ? (a.gmask ? 3 : 2) : (a.mask ? 1 : 0);
   ConvArgs a2 = a;
   a2.t.out_stride = 2;
-  tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, a.t.out_off, mode);
-  tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, a.t.out_off + 1, mode);
+  // (every wave is past the loop's last barrier and the DMA is drained: the stages are free)
+  if (wide) {
+    tile16_wide_epilogue_dispatch(a2, out[0], out[1], smem + __builtin_amdgcn_readfirstlane(wave) * kWideEpiFloats, b, m_base, n0, lane, a.t.out_off,
+                                  a.t.out_off + 1, mode);
+  } else {                                           // a base address off the 16-byte grid: one dword per lane and instruction
+    tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, a.t.out_off, mode);
+    tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, a.t.out_off + 1, mode);
+  }
 
   if (a.stat_part) {                                 // BatchNorm statistics of the output on the way, as in conv_pipe.hip
-    double* red = reinterpret_cast<double*>(smem);   // (every wave is past the loop's last barrier and the DMA is drained: the stages are free)
+    double* red = reinterpret_cast<double*>(smem + RED);      // behind the regions other waves may still be reading
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       const float bias = a.bias ? a.bias[n0 + ct * 16 + n16] : 0.f;
@@ -323,7 +356,8 @@ static int launch_conv_wino(const ConvArgs& a, const float* U, int off0, hipStre
   }
   const int patch = xcd_patch(n_tiles);             // (GN_CONV_NOPATCH is conv_pipe.hip's switch: these kernels always take the patch order)
   prof_begin(s);
-  hipLaunchKernelGGL((conv_wino_kernel<WAVES_M, ABL>), dim3((unsigned)blocks), dim3(64 * WAVES_M), lds, s, a, U, off0, m_tiles, n_tiles, patch);
+  hipLaunchKernelGGL((conv_wino_kernel<WAVES_M, ABL>), dim3((unsigned)blocks), dim3(64 * WAVES_M), lds, s, a, U, off0, m_tiles, n_tiles, patch,
+                     wide_epilogue_aligned(a) ? 1 : 0);
   // flop = what the kernel EXECUTES on the matrix pipe: 6 multiplies per output pair and channel pair, 0.6 of the convolution's algorithmic count
   prof_end(s, 0.6 * 2.0 * a.B * (double)a.M * 5 * a.Cin * a.Cout, 5, 4.0 * ((double)a.B * a.Lin * a.Cin + 5.0 * a.Cin * a.Cout + (double)a.B * a.M * a.Cout));
   int rc = check_launch("conv_wino");

@@ -52,37 +52,38 @@ __global__ void wino_s2_u_kernel(const float* __restrict__ w, float* __restrict_
 }
 
 // slot 0: the next point's U values and the raw rows of the NEXT chunk; row j sits in plane j % NPL at plane row + j / NPL (PB = bytes per plane)
-template <int O, int PB>
+template <int O, int PB, int OA = 0>
 __device__ __forceinline__ void s2_slot_rba7(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b, f32x2 (&d)[7], unsigned addr_a) {
   asm volatile(
       "ds_read_b128 %1, %12 offset:%14\n\t"
       "ds_read_b128 %2, %12 offset:%15\n\t"
-      "ds_read_b64 %3, %13\n\t"
+      "ds_read_b64 %3, %13 offset:%21\n\t"
       "ds_read_b64 %4, %13 offset:%16\n\t"
       "ds_read_b64 %5, %13 offset:%17\n\t"
       "ds_read_b64 %6, %13 offset:%18\n\t"
-      "ds_read_b64 %7, %13 offset:32\n\t"
+      "ds_read_b64 %7, %13 offset:%22\n\t"
       "ds_read_b64 %8, %13 offset:%19\n\t"
       "ds_read_b64 %9, %13 offset:%20\n\t"
       "s_waitcnt lgkmcnt(9)\n\t"
       "v_mfma_f32_16x16x4_f32 %0, %10, %11, %0"
       : "+v"(c), "=&v"(nb0), "=&v"(nb1), "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6])
-      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(PB), "i"(2 * PB), "i"(3 * PB), "i"(PB + 32), "i"(2 * PB + 32)
+      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(OA + PB), "i"(OA + 2 * PB), "i"(OA + 3 * PB), "i"(OA + PB + 32),
+        "i"(OA + 2 * PB + 32), "i"(OA), "i"(OA + 32)
       : "memory");
 }
-template <int O, int PB>
+template <int O, int PB, int OA = 0>
 __device__ __forceinline__ void s2_slot_rba4(f32x4& c, float a, float b, f32x4& nb0, f32x4& nb1, unsigned addr_b, f32x2 (&d)[4], unsigned addr_a) {
   asm volatile(
       "ds_read_b128 %1, %9 offset:%11\n\t"
       "ds_read_b128 %2, %9 offset:%12\n\t"
-      "ds_read_b64 %3, %10\n\t"
+      "ds_read_b64 %3, %10 offset:%15\n\t"
       "ds_read_b64 %4, %10 offset:%13\n\t"
-      "ds_read_b64 %5, %10 offset:32\n\t"
+      "ds_read_b64 %5, %10 offset:%16\n\t"
       "ds_read_b64 %6, %10 offset:%14\n\t"
       "s_waitcnt lgkmcnt(6)\n\t"
       "v_mfma_f32_16x16x4_f32 %0, %7, %8, %0"
       : "+v"(c), "=&v"(nb0), "=&v"(nb1), "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3])
-      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(PB), "i"(PB + 32)
+      : "v"(a), "v"(b), "v"(addr_b), "v"(addr_a), "i"(O), "i"(O + 1024), "i"(OA + PB), "i"(OA + PB + 32), "i"(OA), "i"(OA + 32)
       : "memory");
 }
 // slot 8: its wait also retires the raw rows (issued before the reads this slot adds); they are operands so that their readers depend on it
@@ -112,7 +113,9 @@ __device__ __forceinline__ void s2_slot_rbw4(f32x4& c, float a, float b, f32x4& 
 // 56 MFMA slots per chunk (point p = slot / 8, k-step s = (slot / 4) % 2, column tile ct = slot % 4); conv_wino.hip's choreography with seven points
 // PAR: with SEVEN points the double-buffered U values change parity from chunk to chunk (the next chunk's point 0 is prefetched behind point 6 into the buffer
 // point 7 would use): point p of a chunk of parity PAR lives in B[(p + PAR) & 1]; the chunk loop alternates PAR with its two unrolled halves.
-template <int KIND, int SB, int RPER, int NR, int PAR>
+// OB, OBN, OA: byte offsets of this chunk's stage, of the next chunk's stage (its point-0 U values; its raw rows) inside the asm's immediates, as in
+// conv_wino.hip's WinoChunk
+template <int KIND, int SB, int RPER, int NR, int PAR, int OB = 0, int OBN = 0, int OA = 0>
 struct S2Chunk {
   template <int NPIECES, int I = 0, class D>
   static __device__ __forceinline__ void run(f32x4 (&acc)[7][4], const f32x2 (&v)[7], f32x2 (&vn)[7], f32x2 (&d)[NR], f32x4 (&B)[2][2], unsigned addr_b,
@@ -124,13 +127,13 @@ struct S2Chunk {
       const float bv = bc[CT >> 1][2 * (CT & 1) + S];
       const float av = v[P][S];
       if constexpr (I == 0) {
-        if constexpr (NR == 7) s2_slot_rba7<2048, RPER * 32>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
-        else s2_slot_rba4<2048, RPER * 32>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
+        if constexpr (NR == 7) s2_slot_rba7<OB + 2048, RPER * 32, OA>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
+        else s2_slot_rba4<OB + 2048, RPER * 32, OA>(acc[0][0], av, bv, bn[0], bn[1], addr_b, d, addr_a);
       } else if constexpr (I == 8) {
-        if constexpr (NR == 7) s2_slot_rbw7<2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
-        else s2_slot_rbw4<2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
-      } else if constexpr (I == 48) wino_slot_rb<0, 2>(acc[6][0], av, bv, bn[0], bn[1], addr_b_next);
-      else if constexpr (I % 8 == 0) wino_slot_rb<(P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
+        if constexpr (NR == 7) s2_slot_rbw7<OB + 2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
+        else s2_slot_rbw4<OB + 2 * 2048>(acc[1][0], av, bv, bn[0], bn[1], addr_b, d);
+      } else if constexpr (I == 48) wino_slot_rb<OBN, 2>(acc[6][0], av, bv, bn[0], bn[1], addr_b_next);
+      else if constexpr (I % 8 == 0) wino_slot_rb<OB + (P + 1) * 2048, 2>(acc[P][0], av, bv, bn[0], bn[1], addr_b);
       else wino_slot(acc[P][CT], av, bv);
       if constexpr ((I & 1) && (I >> 1) < NPIECES) dma(std::integral_constant<int, (I >> 1)>{});
       // the seven transform instructions in two runs (a vector instruction alone between two MFMAs of a wave costs 16 cycles, in a run 7: scripts/valu_rate.hip)
@@ -143,7 +146,7 @@ struct S2Chunk {
 
 template <int KIND, int SB>
 __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const float* __restrict__ U, int off0, int m_tiles, int n_tiles, int patch, int offA,
-                                                              int offB) {
+                                                              int offB, int wide) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int KC = 8, NP = 7, WAVES_M = 4;
   constexpr int TT = WAVES_M * 16, TN = 64, NT = 64 * WAVES_M;
@@ -154,6 +157,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
   constexpr int UT = NP * KC * TN;                 // 3584 floats
   constexpr int BUF = SLAB + UT;
   constexpr int STAGE_BYTES = BUF * 4;
+  constexpr int RED = WAVES_M * kWideEpiFloats;    // floats: the epilogue's wave regions lie in front of the statistics' partial sums
+  static_assert(RED * 4 + WAVES_M * TN * 16 <= 3 * STAGE_BYTES, "epilogue regions");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -241,8 +246,27 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
     Bq[0][0] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0));
     Bq[0][1] = *reinterpret_cast<const f32x4*>(sb + (base_b - lds0) + 1024);
   }
-  int st = 0;
-  for (int ch = 0; ch < n_chunks; ch += 2) {
+  int st = 0, ch = 0;
+  // six chunks at a time (stage x parity) with the stage offsets as immediates on the stage-0 addresses, as in conv_wino.hip; the loop below runs the rest
+  static_assert(2 * STAGE_BYTES + 6 * 2048 + 1024 < 65536 && 2 * STAGE_BYTES + 3 * RPER * 32 + 32 < 65536, "stage offsets as ds_read immediates");
+  auto chunk_of_six = [&](auto jc) {
+    constexpr int J = decltype(jc)::value, S0 = J % 3, S1 = (J + 1) % 3, S2 = (J + 2) % 3;
+    c_next = min(ch + J + 2, n_chunks - 1);
+    st_next = S2;
+    using Chunk = S2Chunk<KIND, SB, RPER, NR, J % 2, S0 * STAGE_BYTES, S1 * STAGE_BYTES, S1 * STAGE_BYTES>;
+    if constexpr (J % 2 == 0) Chunk::template run<NPIECES>(acc, V0, V1, d, Bq, base_b, base_b, base_a, dma_piece);
+    else Chunk::template run<NPIECES>(acc, V1, V0, d, Bq, base_b, base_b, base_a, dma_piece);
+    __syncthreads();
+  };
+  for (; ch + 6 <= n_chunks; ch += 6) {
+    chunk_of_six(std::integral_constant<int, 0>{});
+    chunk_of_six(std::integral_constant<int, 1>{});
+    chunk_of_six(std::integral_constant<int, 2>{});
+    chunk_of_six(std::integral_constant<int, 3>{});
+    chunk_of_six(std::integral_constant<int, 4>{});
+    chunk_of_six(std::integral_constant<int, 5>{});
+  }
+  for (; ch < n_chunks; ch += 2) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       if (half == 1 && ch + 1 >= n_chunks) break;
@@ -257,11 +281,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
       st = st1;
     }
   }
-  asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[6][0]), "+v"(acc[6][1]), "+v"(acc[6][2]), "+v"(acc[6][3]));
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 7" : "+v"(acc[6][0]), "+v"(acc[6][1]), "+v"(acc[6][2]), "+v"(acc[6][3]));
 
   const int m_base = t0 + __builtin_amdgcn_readfirstlane(wave) * 16;
   const int mode = a.gy ? (a.gmask ? 3 : 2) : (a.mask ? 1 : 0);
   ConvArgs a2 = a;
+  // the 16-byte epilogue's LDS region of this wave (every wave is past the loop's last barrier and the DMA is drained: the stages are free)
+  float* wreg = smem + __builtin_amdgcn_readfirstlane(wave) * kWideEpiFloats;
   if constexpr (KIND == 1) {
     // both sub-convolutions add into output rows 2 tau and 2 tau + 1
     f32x4 out[2][4];
@@ -273,10 +299,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
         out[1][ct][r] = ((acc[1][ct][r] - acc[2][ct][r]) - acc[3][ct][r]) + (acc[5][ct][r] + acc[6][ct][r]);
       }
     a2.t.out_stride = 2;
-    tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, a.t.out_off, mode);
-    tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, a.t.out_off + 1, mode);
+    if (wide) {
+      tile16_wide_epilogue_dispatch(a2, out[0], out[1], wreg, b, m_base, n0, lane, a.t.out_off, a.t.out_off + 1, mode);
+    } else {                                         // a base address off the 16-byte grid: one dword per lane and instruction
+      tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, a.t.out_off, mode);
+      tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, a.t.out_off + 1, mode);
+    }
     if (a.stat_part) {                               // BatchNorm statistics of the output, as in conv_wino.hip
-      double* red = reinterpret_cast<double*>(smem);
+      double* red = reinterpret_cast<double*>(smem + RED);      // behind the regions other waves may still be reading
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
         const float bias = a.bias ? a.bias[n0 + ct * 16 + n16] : 0.f;
@@ -321,10 +351,15 @@ __global__ __launch_bounds__(256, 2) void conv_wino_s2_kernel(ConvArgs a, const 
         out[3][ct][r] = acc[5][ct][r] + acc[6][ct][r];
       }
     a2.t.out_stride = 4;
-    tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, offA, mode);
-    tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, offA + 2, mode);
-    tile16_epilogue_dispatch<4>(a2, out[2], b, m_base, n0, n16, kq, offB, mode);
-    tile16_epilogue_dispatch<4>(a2, out[3], b, m_base, n0, n16, kq, offB + 2, mode);
+    if (wide) {                                      // in two halves, the 3-tap phase's rows and then the 2-tap phase's: the region holds two tiles
+      tile16_wide_epilogue_dispatch(a2, out[0], out[1], wreg, b, m_base, n0, lane, offA, offA + 2, mode);
+      tile16_wide_epilogue_dispatch(a2, out[2], out[3], wreg, b, m_base, n0, lane, offB, offB + 2, mode);
+    } else {
+      tile16_epilogue_dispatch<4>(a2, out[0], b, m_base, n0, n16, kq, offA, mode);
+      tile16_epilogue_dispatch<4>(a2, out[1], b, m_base, n0, n16, kq, offA + 2, mode);
+      tile16_epilogue_dispatch<4>(a2, out[2], b, m_base, n0, n16, kq, offB, mode);
+      tile16_epilogue_dispatch<4>(a2, out[3], b, m_base, n0, n16, kq, offB + 2, mode);
+    }
   }
 #endif
 }
@@ -347,7 +382,8 @@ static int launch_s2(const ConvArgs& a, const float* U, int off0, int offA, int 
   }
   const int patch = xcd_patch(n_tiles);             // (GN_CONV_NOPATCH is conv_pipe.hip's switch: these kernels always take the patch order)
   prof_begin(s);
-  hipLaunchKernelGGL((conv_wino_s2_kernel<KIND, SB>), dim3((unsigned)blocks), dim3(256), lds, s, a, U, off0, m_tiles, n_tiles, patch, offA, offB);
+  hipLaunchKernelGGL((conv_wino_s2_kernel<KIND, SB>), dim3((unsigned)blocks), dim3(256), lds, s, a, U, off0, m_tiles, n_tiles, patch, offA, offB,
+                     wide_epilogue_aligned(a) ? 1 : 0);
   // flop = what the kernel EXECUTES: 7 multiplies per output pair and channel, 0.7 of the convolution's algorithmic count (kind 7)
   prof_end(s, 0.7 * 2.0 * a.B * (double)a.M * 5 * a.Cin * a.Cout, 7, 4.0 * ((double)a.B * a.Lin * a.Cin + 5.0 * a.Cin * a.Cout + (double)a.B * a.M * a.Cout));
   int rc = check_launch("conv_wino_s2");
