@@ -9,6 +9,8 @@ Mirrors the Keras 2.2.4 surface that BBH_version/bbhMahoGANy.py uses (SURVEY sec
   * train_on_batch(x, y) -> [loss, *metrics] python floats, keras ordering for multi-output models (:1165, :1292, :1296)
   * every Keras loss name / alias / keras.losses callable, loss_weights=[...], several metrics; test_on_batch, evaluate, predict_on_batch
     (ops.loss_pass); sample_weight=, class_weight=, compile(weighted_metrics=) (ops.loss_pass_weighted; section 8f)
+  * keras.regularizers on weights (*_regularizer keywords) and outputs (activity_regularizer, ActivityRegularization): their penalties in
+    entry 0 of train_on_batch / test_on_batch / evaluate, their gradient terms before the optimizer's clipping (ops.reg_pass; section 8l)
   * predict(x) -> ndarray | [ndarray] (default batch_size 32) (:1185, :1248, :1343); learning phase 1 in train_on_batch for
     the WHOLE graph, 0 in predict
   * save / save_weights / load_weights / load_model (:1135-1142, :1173, :1373-1375)
@@ -80,8 +82,9 @@ class Param(object):
     """A weight tensor.  The initial value stays on the host until the first device access, so graphs can be built,
     planned and inspected (summary, count_params, get_weights) on a machine without a GPU; all arithmetic needs one."""
 
-    def __init__(self, name, value, trainable=True):
+    def __init__(self, name, value, trainable=True, regularizer=None):
         self.name = name
+        self.regularizer = regularizer     # a regularizers.L1L2 or None: its penalty enters the loss of every model that holds the weight (DESIGN 8l)
         self.shape = tuple(value.shape)
         self._host = np.ascontiguousarray(value, np.float32)
         self._data = None
@@ -324,6 +327,8 @@ class RunContext(object):
         self.pre_applied = set()           # producers whose activation gradient has already been applied to their dy
         self.skip = set()                  # inference phase: BatchNormalization nodes already folded into the producing conv
         self.bn_sums = {}                  # training phase: BN node index -> fp64 (sum x, sum x^2) produced by the conv epilogue
+        self.reg = None                    # train / test step of a regularized model: node index -> its slice of the step's fp64 penalty partials
+        self.reg_y = {}                    # training phase: node index -> the output an activity regularizer's gradient term is formed from
 
     def wants_grad(self, layer):
         if self.train_ids is None:
@@ -379,8 +384,8 @@ class Layer(object):
         self.buffers = []
 
     # -- keras-style weight bookkeeping
-    def add_weight(self, name, value, trainable=True):
-        p = Param('%s/%s' % (self.name, name), value, trainable)
+    def add_weight(self, name, value, trainable=True, regularizer=None):
+        p = Param('%s/%s' % (self.name, name), value, trainable, regularizer)
         (self.params if trainable else self.buffers).append(p)
         return p
 
@@ -474,6 +479,7 @@ class Layer(object):
     fusable_act = False      # can take an activation epilogue
     fusable_drop = False     # can take a dropout epilogue
     act_spec = None          # (kind, param) if this layer IS an activation
+    activity_regularizer = None   # a regularizers.L1L2 on this layer's own output (Dense, the conv layers, ActivityRegularization)
     drop_rate = None         # rate if this layer IS a dropout
 
     def writes_dy(self, node):
@@ -958,8 +964,13 @@ class Model(Layer):
                 return None
             return self.nodes[consumers[i][0]]
 
+        # a node with an activity regularizer: the penalty is taken of the layer's OWN output, so that tensor is materialised as the
+        # layer defines it -- no epilogue of a following layer is fused onto it, forward or backward, in either phase
+        def areg(node):
+            return node.layer.activity_regularizer is not None
+
         for n in self.nodes:
-            if n.absorbed:
+            if n.absorbed or areg(n):
                 continue
             tail = n
             # a layer with a non-linear activation of its own (Dense, Conv1D, Conv2D, Conv2DTranspose(activation=...)) has its epilogue taken: an
@@ -982,13 +993,13 @@ class Model(Layer):
             if n.absorbed or not getattr(n.layer, 'is_upsample2', False) or len(n.inbound) != 1 or n.inbound[0] < 0:
                 continue
             c = sole_consumer(n.index)
-            if c is not None and not c.absorbed and hasattr(c.layer, 'can_fold_upsample') and c.layer.can_fold_upsample():
+            if c is not None and not c.absorbed and not areg(c) and hasattr(c.layer, 'can_fold_upsample') and c.layer.can_fold_upsample():
                 c.fold_up = n
                 n.absorbed = True
         # inference-phase fusion: a BatchNormalization that is the sole consumer of a linear conv folds into that conv's weights
         # (predict only: the training phase normalises with batch statistics)
         for n in self.nodes:
-            if n.absorbed or not getattr(n.layer, 'can_fold_bn', False) or n.fused_act is not None or n.fused_drop is not None:
+            if n.absorbed or areg(n) or not getattr(n.layer, 'can_fold_bn', False) or n.fused_act is not None or n.fused_drop is not None:
                 continue
             c = sole_consumer(n.index)
             if c is not None and getattr(c.layer, 'is_batchnorm', False):
@@ -1004,7 +1015,8 @@ class Model(Layer):
                     ok = False
                     break
                 cur = self.nodes[cur].inbound[0]
-            if ok and cur >= 0 and len(consumers[cur]) == 1 and cur not in outs and getattr(self.nodes[cur].layer, 'offers_act_bwd', False):
+            if (ok and cur >= 0 and len(consumers[cur]) == 1 and cur not in outs and getattr(self.nodes[cur].layer, 'offers_act_bwd', False)
+                    and not areg(self.nodes[cur])):
                 n.fuse_prev = cur
         # a 1-filter stride-1 Conv1D whose input comes from a BatchNormalization through absorbed nodes only (the generator's output
         # conv): its data gradient is not materialised, the BatchNormalization's backward passes form it on the fly (ops.ConvGrad1)
@@ -1034,6 +1046,13 @@ class Model(Layer):
                 vals[n.index] = xs[0]
                 continue
             vals[n.index] = n.layer.forward(ctx, n, xs[0] if len(xs) == 1 else xs)
+            if ctx.reg is not None and n.layer.activity_regularizer is not None:
+                # the activity penalty of the layer's own output (this rank's rows): block partials into the step's slice; the training phase
+                # keeps the output for the gradient term of the backward sweep (predict has no ctx.reg: it never adds a penalty)
+                y, r = vals[n.index].contiguous(), n.layer.activity_regularizer
+                ops.reg_pass(y, None, r.l1, r.l2, ctx.reg[n.index])
+                if ctx.training:
+                    ctx.reg_y[n.index] = y
             if ctx.capture is not None:
                 ctx.capture[n.layer.name] = vals[n.index]
         return [vals[i] for i in self.output_ids]
@@ -1077,6 +1096,11 @@ class Model(Layer):
             dy = take(n.index)
             if dy is None:
                 continue
+            if n.index in ctx.reg_y:
+                # activity regularizer: l1 sign(y) + 2 l2 y joins the gradient arriving at the layer's output, in place unless another
+                # pending edge still holds that storage
+                y, r = ctx.reg_y.pop(n.index), n.layer.activity_regularizer
+                dy = ops.reg_grad(y, dy.contiguous().view(y.shape), r.l1, r.l2, inplace=key(dy) not in held)
             if n.absorbed:
                 dxs = [dy]
             else:
@@ -1156,6 +1180,14 @@ class Model(Layer):
                         if id(p) not in seen:
                             seen.add(id(p)); params.append(p)
         self._train_params = params
+        # regularizers, as keras' Network.losses collects them: every weight of every layer of the model that carries one, spliced-in
+        # models and frozen layers included (a frozen weight: penalty only), each weight once; every node whose layer regularizes its output
+        self._reg_params, regd = [], set()
+        for n in self.nodes:
+            for p in n.layer.weights:
+                if p.regularizer is not None and id(p) not in regd:
+                    regd.add(id(p)); self._reg_params.append((p, id(p) in seen))
+        self._reg_nodes = [n for n in self.nodes if n.layer.activity_regularizer is not None]
         self._bound = False                # flat grouping + optimizer state are created at the first device step
         if data_parallel is not None:
             self.data_parallel = data_parallel
@@ -1291,6 +1323,7 @@ class Model(Layer):
             row_map = ([(dp.rank * B, B)], B * world)
         ctx = RunContext(True, dp, masks, self._train_params, self.name, row_map)
         ctx.capture = capture
+        reg = self._reg_begin(ctx, B)
         outs = self._forward(xs, ctx)
         dps, stats = self._loss_stats(outs, ys, B, world, True, sample_weights)
         for grp, a, b in segments(self._train_params):
@@ -1301,8 +1334,43 @@ class Model(Layer):
             for grp, a, b in segments(self._train_params):
                 dp.all_reduce_sum(grp.grad[a:b])
             dp.all_reduce_sum(stats)
+        if reg is not None:                # after the all-reduce (the gradients are the global mean), before the optimizer's clipping sees them
+            stats = self._reg_end(reg, stats, True)
         self.optimizer.step()
         return stats
+
+    # -- regularizers.  A model without any never enters these: reg is None, its launches and its statistics tensor are unchanged.
+    def _reg_begin(self, ctx, B):
+        """The step's fp64 penalty partials, one slice per regularized weight and then one per activity-regularized node (ctx.reg: the forward
+        sweep fills those).  The slice sizes depend on the tensor sizes alone (ops.reg_partials).  None for a model without regularizers."""
+        if not self._reg_params and not self._reg_nodes:
+            return None
+        off, wsl, asl = 0, [], []
+        for p, _ in self._reg_params:
+            k = ops.reg_partials(p.size)
+            wsl.append((off, k)); off += k
+        w_end = off
+        for n in self._reg_nodes:
+            k = ops.reg_partials(B * int(np.prod(n.out_shape)))
+            asl.append((n.index, off, k)); off += k
+        parts = torch.zeros(off, dtype=torch.float64, device=device())     # zeros: a slice no pass reached would add nothing
+        ctx.reg = dict((i, parts[a:a + k]) for i, a, k in asl)
+        return parts, wsl, w_end
+
+    def _reg_end(self, reg, stats, train):
+        """One pass per regularized weight: its penalty partials and, in a training step, its gradient term l1 sign(w) + 2 l2 w added ONCE to
+        the (already all-reduced) gradient of a weight this model trains; a frozen weight, and every weight in the test phase: penalty only.
+        The activity partials are this rank's sums: all-reduced beside the statistics.  Then one fixed-order sum of everything, on the device;
+        it returns the statistics with one more row, [penalty, 0, ...], which train_result adds to entry 0."""
+        parts, wsl, w_end = reg
+        dp = self.data_parallel
+        if dp is not None and parts.numel() > w_end:
+            dp.all_reduce_sum(parts[w_end:])
+        for (p, trained), (a, k) in zip(self._reg_params, wsl):
+            ops.reg_pass(p.data, p.grad if train and trained else None, p.regularizer.l1, p.regularizer.l2, parts[a:a + k])
+        row = torch.zeros((1, stats.shape[1]), dtype=torch.float32, device=stats.device)
+        ops.reg_finish(parts, row[0, :1])
+        return torch.cat([stats, row])
 
     def _loss_stats(self, outs, ys, B, world, grad, sws=None):
         """Per output: the loss (with its gradient when `grad`) and the compiled metrics, all on the device.  Returns (gradients, the
@@ -1379,10 +1447,14 @@ class Model(Layer):
         B = xs[0].shape[0]
         dp = self.data_parallel
         world = dp.world_size if dp is not None else 1
-        outs = self._forward(xs, RunContext(False))
+        ctx = RunContext(False)
+        reg = self._reg_begin(ctx, B)      # keras adds the penalties in the test phase too (never in predict)
+        outs = self._forward(xs, ctx)
         stats = torch.stack(self._loss_stats(outs, ys, B, world, False, sample_weights)[1])
         if dp is not None:
             dp.all_reduce_sum(stats)
+        if reg is not None:
+            stats = self._reg_end(reg, stats, False)
         return stats
 
     def evaluate(self, x, y, batch_size=32, verbose=0, sample_weight=None):
@@ -1414,8 +1486,12 @@ class Model(Layer):
         """[loss, (per-output losses,) (accuracies)] as python floats, keras order, from train_on_batch_device's statistics (one device -> host read)."""
         world = self.data_parallel.world_size if self.data_parallel is not None else 1
         st = stats.cpu().numpy().astype(np.float64)
+        penalty = 0.0
+        if st.shape[0] == len(self.output_ids) + 1:        # a regularized model: the last row holds the sum of all penalties (_reg_end)
+            penalty, st = float(st[-1, 0]), st[:-1]
         losses = [float(v) * sc for v, sc in zip(st[:, 0], self._loss_scales)]
-        res = [float(sum(l * w for l, w in zip(losses, self._loss_w)))]       # per-output entries stay unweighted, as keras reports them
+        # per-output entries stay unweighted, as keras reports them; the penalties enter entry 0 alone, once
+        res = [float(sum(l * w for l, w in zip(losses, self._loss_w))) + penalty]
         if len(losses) > 1:
             res += losses
         cols = [int(np.prod(self.nodes[i].out_shape)) for i in self.output_ids]

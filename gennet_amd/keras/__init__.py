@@ -7,6 +7,7 @@
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU, Softmax
     from gennet_amd.keras.activations import softmax, relu, tanh, sigmoid, linear            # names for activation=
+    from gennet_amd.keras import regularizers                          # l1, l2, l1_l2, L1L2, get, serialize, deserialize
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, add, concatenate, ...                # all seven merge layers and functions
@@ -27,6 +28,7 @@ import types
 
 from .. import engine as _engine
 from .. import layers as _layers
+from .. import regularizers as _regularizers
 from . import backend  # noqa: F401
 
 
@@ -56,7 +58,7 @@ def _pick(mod, *names):
     return dict((n, getattr(mod, n)) for n in names)
 
 
-_core = _pick(_layers, 'Activation', 'Dense', 'Dropout', 'Flatten', 'Reshape')
+_core = _pick(_layers, 'Activation', 'ActivityRegularization', 'Dense', 'Dropout', 'Flatten', 'Reshape')
 _norm = _pick(_layers, 'BatchNormalization')
 _conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'UpSampling1D', 'MaxPooling2D'),
              **_unused('37-38', 'UpSampling2D'))
@@ -77,6 +79,7 @@ _TREE = {
     'models': _pick(_engine, 'Model', 'Sequential', 'load_model', 'model_from_json'),
     'optimizers': dict(_pick(_engine, 'Adam', 'SGD', 'RMSprop', 'Adagrad', 'Adadelta', 'Adamax'), **_unused('43', 'Nadam')),
     'activations': dict(_layers.ACTIVATIONS),
+    'regularizers': _pick(_regularizers, 'Regularizer', 'L1L2', 'l1', 'l2', 'l1_l2', 'serialize', 'deserialize', 'get'),
     'engine': {},
     'engine.topology': _pick(_engine, 'Layer'),
     'layers': _top,

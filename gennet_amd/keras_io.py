@@ -20,6 +20,7 @@ import json
 import numpy as np
 
 from . import h5lite
+from .regularizers import serialize as _reg
 from .engine import Adam, Input, Layer, Model, Sequential, optimizer_from_config, to_snake_case  # noqa: F401
 
 KERAS_VERSION = '2.2.4'
@@ -168,9 +169,11 @@ _ONES = {'class_name': 'Ones', 'config': {}}
 _ACT_OF_SPEC = {'relu': 'relu', 'tanh': 'tanh', 'sigmoid': 'sigmoid', 'linear': 'linear', 'softmax': 'softmax'}
 
 
-def _kernel_part():
-    return {'use_bias': True, 'kernel_initializer': _GLOROT, 'bias_initializer': _ZEROS, 'kernel_regularizer': None, 'bias_regularizer': None,
-            'activity_regularizer': None, 'kernel_constraint': None, 'bias_constraint': None}
+def _kernel_part(layer):
+    """the keys Dense and the conv layers share; a regularizer as keras serializes it: {'class_name': 'L1L2', 'config': {'l1', 'l2'}} or None"""
+    return {'use_bias': True, 'kernel_initializer': _GLOROT, 'bias_initializer': _ZEROS, 'kernel_regularizer': _reg(layer.kernel_regularizer),
+            'bias_regularizer': _reg(layer.bias_regularizer), 'activity_regularizer': _reg(layer.activity_regularizer), 'kernel_constraint': None,
+            'bias_constraint': None}
 
 
 def layer_config(layer):
@@ -180,23 +183,23 @@ def layer_config(layer):
         cfg['batch_input_shape'] = [None] + list(layer.input_shape_arg)
         cfg['dtype'] = 'float32'
     if isinstance(layer, L.Dense):
-        cfg.update(units=layer.units, activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+        cfg.update(units=layer.units, activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part(layer))
     elif isinstance(layer, L.Conv1D):
         cfg.update(filters=layer.filters, kernel_size=[layer.k], strides=[layer.stride], padding=layer.padding, data_format='channels_last',
-                   dilation_rate=[layer.dilation], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+                   dilation_rate=[layer.dilation], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part(layer))
     elif isinstance(layer, L.Conv2DTranspose):
         # the keys (and values) keras 2.1.6 wrote for the reference's g_model.hdf5: no dilation_rate / output_padding
         cfg.update(filters=layer.filters, kernel_size=[1, layer.k], strides=[1, layer.stride], padding=layer.padding, data_format='channels_last',
-                   activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+                   activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part(layer))
     elif isinstance(layer, L.Conv2D):
         cfg.update(filters=layer.filters, kernel_size=[layer.kh, layer.kw], strides=[layer.sh, layer.sw], padding=layer.padding,
-                   data_format='channels_last', dilation_rate=[1, 1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part())
+                   data_format='channels_last', dilation_rate=[1, 1], activation=_ACT_OF_SPEC[layer.activation[0]], **_kernel_part(layer))
     elif isinstance(layer, L.BatchNormalization):
         cfg.update(axis=layer.axis, momentum=layer.momentum, epsilon=layer.epsilon, center=True, scale=True, beta_initializer=_ZEROS, gamma_initializer=_ONES,
-                   moving_mean_initializer=_ZEROS, moving_variance_initializer=_ONES, beta_regularizer=None, gamma_regularizer=None,
+                   moving_mean_initializer=_ZEROS, moving_variance_initializer=_ONES, beta_regularizer=_reg(layer.beta_regularizer), gamma_regularizer=_reg(layer.gamma_regularizer),
                    beta_constraint=None, gamma_constraint=None)
     elif isinstance(layer, L.PReLU):
-        cfg.update(alpha_initializer=_ZEROS, alpha_regularizer=None, alpha_constraint=None, shared_axes=None)
+        cfg.update(alpha_initializer=_ZEROS, alpha_regularizer=_reg(layer.alpha_regularizer), alpha_constraint=None, shared_axes=None)
     elif isinstance(layer, L.LeakyReLU):
         cfg.update(alpha=layer.act_spec[1])
     elif isinstance(layer, L.ReLU):
@@ -205,6 +208,8 @@ def layer_config(layer):
         cfg.update(activation='softmax' if layer.softmax else _ACT_OF_SPEC[layer.act_spec[0]])
     elif isinstance(layer, L.Softmax):
         cfg.update(axis=layer.axis)
+    elif isinstance(layer, L.ActivityRegularization):
+        cfg.update(l1=layer.l1, l2=layer.l2)
     elif isinstance(layer, L.Dropout):
         cfg.update(rate=layer.rate, noise_shape=None, seed=None)
     elif isinstance(layer, L.GaussianNoise):
@@ -280,28 +285,33 @@ def _layer_from_config(class_name, cfg, custom_objects):
             return
         raise NotImplementedError('kernel_initializer %r' % (c,))
 
+    def regs(*keys):                       # the layer constructors take the config dicts as they are (regularizers.get)
+        return dict((k, cfg.get(k)) for k in keys)
+    kregs = regs('kernel_regularizer', 'bias_regularizer', 'activity_regularizer')
+
     if class_name == 'Dense':
         init_ok(cfg.get('kernel_initializer'))
-        return L.Dense(cfg['units'], activation=cfg.get('activation'), use_bias=cfg.get('use_bias', True), **kw)
+        return L.Dense(cfg['units'], activation=cfg.get('activation'), use_bias=cfg.get('use_bias', True), **kregs, **kw)
     if class_name == 'Conv1D':
         init_ok(cfg.get('kernel_initializer'))
         return L.Conv1D(cfg['filters'], cfg['kernel_size'], strides=cfg.get('strides', 1), padding=cfg.get('padding', 'valid'), activation=cfg.get('activation'),
-                        use_bias=cfg.get('use_bias', True), dilation_rate=cfg.get('dilation_rate', 1), **kw)
+                        use_bias=cfg.get('use_bias', True), dilation_rate=cfg.get('dilation_rate', 1), **kregs, **kw)
     if class_name == 'Conv2D':
         init_ok(cfg.get('kernel_initializer'))
         return L.Conv2D(cfg['filters'], tuple(cfg['kernel_size']), strides=tuple(cfg.get('strides', (1, 1))), padding=cfg.get('padding', 'valid'),
-                        activation=cfg.get('activation'), use_bias=cfg.get('use_bias', True), **kw)
+                        activation=cfg.get('activation'), use_bias=cfg.get('use_bias', True), **kregs, **kw)
     if class_name == 'Conv2DTranspose':
         init_ok(cfg.get('kernel_initializer'))
         dil = cfg.get('dilation_rate', [1, 1])
         return L.Conv2DTranspose(cfg['filters'], tuple(cfg['kernel_size']), strides=tuple(cfg.get('strides', (1, 1))), padding=cfg.get('padding', 'valid'),
                                  output_padding=cfg.get('output_padding'), data_format=cfg.get('data_format'),
                                  dilation_rate=tuple(dil) if isinstance(dil, (list, tuple)) else dil, activation=cfg.get('activation'),
-                                 use_bias=cfg.get('use_bias', True), **kw)
+                                 use_bias=cfg.get('use_bias', True), **kregs, **kw)
     if class_name == 'BatchNormalization':
-        return L.BatchNormalization(axis=cfg.get('axis', -1), momentum=cfg.get('momentum', 0.99), epsilon=cfg.get('epsilon', 1e-3), **kw)
+        return L.BatchNormalization(axis=cfg.get('axis', -1), momentum=cfg.get('momentum', 0.99), epsilon=cfg.get('epsilon', 1e-3),
+                                    **regs('beta_regularizer', 'gamma_regularizer'), **kw)
     if class_name == 'PReLU':
-        return L.PReLU(alpha_initializer=cfg.get('alpha_initializer', 'zeros'), shared_axes=cfg.get('shared_axes'), **kw)
+        return L.PReLU(alpha_initializer=cfg.get('alpha_initializer', 'zeros'), shared_axes=cfg.get('shared_axes'), **regs('alpha_regularizer'), **kw)
     if class_name == 'LeakyReLU':
         return L.LeakyReLU(alpha=cfg.get('alpha', 0.3), **kw)
     if class_name == 'ReLU':
@@ -310,6 +320,8 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.Activation(cfg['activation'], **kw)
     if class_name == 'Softmax':
         return L.Softmax(axis=cfg.get('axis', -1), **kw)
+    if class_name == 'ActivityRegularization':
+        return L.ActivityRegularization(l1=cfg.get('l1', 0.), l2=cfg.get('l2', 0.), **kw)
     if class_name == 'Dropout':
         return L.Dropout(cfg['rate'], **kw)
     if class_name == 'GaussianNoise':

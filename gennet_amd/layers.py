@@ -10,7 +10,7 @@ import collections
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, regularizers
 from .engine import Layer, Model, capturing, device, device_rng, glorot_uniform
 
 import os as _os
@@ -66,6 +66,12 @@ def _channel_softmax(layer, y):
 def _check_init(kernel_initializer):
     if kernel_initializer not in (None, 'glorot_uniform'):
         raise NotImplementedError('kernel_initializer %r (only glorot_uniform is used on the hot path)' % (kernel_initializer,))
+
+
+def _take_regularizers(layer, kernel, bias, activity):
+    """the three regularizer keywords of Dense and the conv layers, through regularizers.get (an L1L2, 'l1' / 'l2' / 'l1_l2', a config dict, None)"""
+    layer.kernel_regularizer, layer.bias_regularizer = regularizers.get(kernel), regularizers.get(bias)
+    layer.activity_regularizer = regularizers.get(activity)
 
 
 def _conv_fwd(node, ctx, x, w, b, stride, pl, Lout, act, out_shape_for_mask, any_channels=False, drop_ok=True):
@@ -196,9 +202,11 @@ class Dense(Layer):
         k = getattr(self, 'kernel', None)          # the fused small-output backward needs an input width that is a multiple of 4
         return self.units <= 4 and (k is None or k.shape[0] % 4 == 0)
 
-    def __init__(self, units, activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
+    def __init__(self, units, activation=None, kernel_initializer='glorot_uniform', use_bias=True, kernel_regularizer=None, bias_regularizer=None,
+                 activity_regularizer=None, **kw):
         Layer.__init__(self, **kw)
         _check_init(kernel_initializer)
+        _take_regularizers(self, kernel_regularizer, bias_regularizer, activity_regularizer)
         if not use_bias:
             raise NotImplementedError('Dense(use_bias=False)')
         self.units = int(units)
@@ -206,8 +214,8 @@ class Dense(Layer):
 
     def build(self, input_shape):
         assert len(input_shape) == 1, 'Dense expects (batch, features); Flatten first'
-        self.kernel = self.add_weight('kernel', glorot_uniform((input_shape[0], self.units)))
-        self.bias = self.add_weight('bias', np.zeros(self.units, np.float32))
+        self.kernel = self.add_weight('kernel', glorot_uniform((input_shape[0], self.units)), regularizer=self.kernel_regularizer)
+        self.bias = self.add_weight('bias', np.zeros(self.units, np.float32), regularizer=self.bias_regularizer)
 
     def compute_output_shape(self, input_shape):
         return (self.units,)
@@ -276,9 +284,10 @@ class Conv1D(Layer):
         return not any(_ConvRun(self, k.shape[1], up).any_channels for up in ((False, True) if self.can_fold_upsample() else (False,)))
 
     def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True,
-                 dilation_rate=1, **kw):
+                 dilation_rate=1, kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, **kw):
         Layer.__init__(self, **kw)
         _check_init(kernel_initializer)
+        _take_regularizers(self, kernel_regularizer, bias_regularizer, activity_regularizer)
         if not use_bias:
             raise NotImplementedError('Conv1D(use_bias=False)')
         self.filters = int(filters)
@@ -315,8 +324,8 @@ class Conv1D(Layer):
             raise NotImplementedError('Conv1D(%d filters, strides=%d) on %d input channels: strides above 2 run on the small-Cin kernels only, which '
                                       'need a multiple of 4 filters; the any-channel kernels implement strides 1 and 2'
                                       % (self.filters, self.stride, Cin))
-        self.kernel = self.add_weight('kernel', glorot_uniform((self.k, Cin, self.filters)))
-        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
+        self.kernel = self.add_weight('kernel', glorot_uniform((self.k, Cin, self.filters)), regularizer=self.kernel_regularizer)
+        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32), regularizer=self.bias_regularizer)
 
     def compute_output_shape(self, input_shape):
         return (ops.conv_geometry(input_shape[0], self.k, self.stride, self.padding, self.dilation)[0], self.filters)
@@ -436,9 +445,11 @@ class Conv2D(Layer):
 
     offers_act_bwd = fusable_drop
 
-    def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True, **kw):
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True,
+                 kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, **kw):
         Layer.__init__(self, **kw)
         _check_init(kernel_initializer)
+        _take_regularizers(self, kernel_regularizer, bias_regularizer, activity_regularizer)
         self.filters = int(filters)
         self.kh, self.kw = (kernel_size, kernel_size) if isinstance(kernel_size, int) else tuple(kernel_size)
         self.sh, self.sw = (strides, strides) if isinstance(strides, int) else tuple(strides)
@@ -451,8 +462,8 @@ class Conv2D(Layer):
         H, W, Cin = input_shape
         if W != 2:
             raise NotImplementedError('Conv2D is implemented for width-2 images (got width %d)' % W)
-        self.kernel = self.add_weight('kernel', glorot_uniform((self.kh, self.kw, Cin, self.filters)))
-        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
+        self.kernel = self.add_weight('kernel', glorot_uniform((self.kh, self.kw, Cin, self.filters)), regularizer=self.kernel_regularizer)
+        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32), regularizer=self.bias_regularizer)
 
     def compute_output_shape(self, input_shape):
         return (ops.conv_geometry(input_shape[0], self.kh, self.sh, 'same')[0], 2, self.filters)
@@ -513,9 +524,11 @@ class Conv2DTranspose(Layer):
         return not _is_softmax(self)
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', output_padding=None, data_format=None, dilation_rate=(1, 1),
-                 activation=None, use_bias=True, kernel_initializer='glorot_uniform', **kw):
+                 activation=None, use_bias=True, kernel_initializer='glorot_uniform', kernel_regularizer=None, bias_regularizer=None,
+                 activity_regularizer=None, **kw):
         Layer.__init__(self, **kw)
         _check_init(kernel_initializer)
+        _take_regularizers(self, kernel_regularizer, bias_regularizer, activity_regularizer)
         self.filters = int(filters)
         kh, self.k = _pair(kernel_size, 'kernel_size')
         sh, self.stride = _pair(strides, 'strides')
@@ -541,8 +554,8 @@ class Conv2DTranspose(Layer):
             raise NotImplementedError('Conv2DTranspose(%d filters, kernel (1, %d)) on %d input channels: the conv kernels need both channel counts '
                                       'multiples of 4, or one of them <= 4 and the other a multiple of 4' % (self.filters, self.k, input_shape[2]))
         # keras' layout (1, kw, filters, Cin): glorot limit sqrt(6 / ((filters + Cin) kw)), and .h5 reads / writes are plain copies
-        self.kernel = self.add_weight('kernel', glorot_uniform((1, self.k, self.filters, input_shape[2])))
-        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32))
+        self.kernel = self.add_weight('kernel', glorot_uniform((1, self.k, self.filters, input_shape[2])), regularizer=self.kernel_regularizer)
+        self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32), regularizer=self.bias_regularizer)
 
     def out_length(self, W):
         """keras deconv_length (conv_utils.py) for 'valid' / 'same' without output_padding."""
@@ -617,8 +630,9 @@ class BatchNormalization(Layer):
     (layer, training model).  The pairs are not keras weights: real keras never writes them to .h5 files and starts them from zero
     after load_weights; keras_io keeps them in a private section of files written here.
     moving_average = 'ema': the plain exponential average (zero_debias=False; what tf.keras and later keras versions do)."""
-    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, moving_average=None, **kw):
+    def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, moving_average=None, beta_regularizer=None, gamma_regularizer=None, **kw):
         Layer.__init__(self, **kw)
+        self.beta_regularizer, self.gamma_regularizer = regularizers.get(beta_regularizer), regularizers.get(gamma_regularizer)
         if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
             raise NotImplementedError('BatchNormalization(axis=%r): one integer axis' % (axis,))
         self.axis = int(axis)              # keras' axis, counting the batch dimension; written back as given (keras_io)
@@ -646,8 +660,8 @@ class BatchNormalization(Layer):
         C = int(input_shape[k])
         self.view = (int(np.prod(input_shape[:k], dtype=np.int64)), C, int(np.prod(input_shape[k + 1:], dtype=np.int64)))
         self._last_axis = k == len(input_shape) - 1
-        self.gamma = self.add_weight('gamma', np.ones(C, np.float32))
-        self.beta = self.add_weight('beta', np.zeros(C, np.float32))
+        self.gamma = self.add_weight('gamma', np.ones(C, np.float32), regularizer=self.gamma_regularizer)
+        self.beta = self.add_weight('beta', np.zeros(C, np.float32), regularizer=self.beta_regularizer)
         self.moving_mean = self.add_weight('moving_mean', np.zeros(C, np.float32), trainable=False)
         self.moving_variance = self.add_weight('moving_variance', np.ones(C, np.float32), trainable=False)
 
@@ -889,8 +903,9 @@ class PReLU(Layer):
     """keras.layers.PReLU() (bbhMahoGANy.py:39; the act = 'prelu' branches of generator_model, :237-286): one learnable slope per
     feature of a sample (no shared axes), initialised to zero; y = x > 0 ? x : alpha * x."""
 
-    def __init__(self, alpha_initializer='zeros', shared_axes=None, **kw):
+    def __init__(self, alpha_initializer='zeros', shared_axes=None, alpha_regularizer=None, **kw):
         Layer.__init__(self, **kw)
+        self.alpha_regularizer = regularizers.get(alpha_regularizer)
         if alpha_initializer not in ('zeros', None) and not (isinstance(alpha_initializer, dict) and alpha_initializer.get('class_name') == 'Zeros'):
             raise NotImplementedError('PReLU(alpha_initializer=%r)' % (alpha_initializer,))
         if shared_axes:
@@ -899,7 +914,7 @@ class PReLU(Layer):
     def build(self, input_shape):
         if int(np.prod(input_shape)) % 4:
             raise NotImplementedError('PReLU on %r: the feature count must be a multiple of 4' % (tuple(input_shape),))
-        self.alpha = self.add_weight('alpha', np.zeros(tuple(input_shape), np.float32))
+        self.alpha = self.add_weight('alpha', np.zeros(tuple(input_shape), np.float32), regularizer=self.alpha_regularizer)
 
     def forward(self, ctx, node, x):
         x = x.contiguous()
@@ -910,6 +925,24 @@ class PReLU(Layer):
         x = ctx.tape.pop(node.index)
         dx, _ = ops.prelu_bwd(dy.contiguous(), x, self.alpha.data, need_dx or not need_dw, self.alpha.grad if need_dw else None)
         return dx
+
+
+class ActivityRegularization(Layer):
+    """keras.layers.ActivityRegularization(l1=0., l2=0.): the identity, whose output carries the activity regularizer L1L2(l1, l2).  The penalty and
+    its gradient term are the engine's (Model._forward / _backward); the layer itself launches nothing.  With both coefficients zero it
+    regularizes nothing and no pass runs."""
+
+    def __init__(self, l1=0., l2=0., **kw):
+        Layer.__init__(self, **kw)
+        reg = regularizers.L1L2(l1=l1, l2=l2)
+        self.l1, self.l2 = reg.l1, reg.l2
+        self.activity_regularizer = regularizers.active(reg)
+
+    def forward(self, ctx, node, x):
+        return x
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        return dy
 
 
 class Dropout(Layer):

@@ -1094,6 +1094,38 @@ def optim_clip_factor(partials, clipnorm, factor):
     _lib.call('gn_optim_clip_factor', _p(partials), partials.numel(), float(clipnorm), _p(factor), _stream())
 
 
+# ---------------------------------------------------------------------------------------------- regularizers (csrc/regularizer.hip)
+@functools.lru_cache(maxsize=None)
+def reg_partials(n):
+    """fp64 partials that reg_pass writes for a tensor of n floats (a function of n alone)."""
+    return _lib.size('gn_reg_partials', int(n))
+
+
+def reg_pass(x, g, l1, l2, partials):
+    """Penalty and gradient of one regularized tensor in one read of x: partials[:reg_partials(x.numel())] = fp64 block partials of
+    l1 sum|x| + l2 sum x^2, and g += l1 sign(x) + 2 l2 x (sign(+-0) = 0) unless g is None (penalty only)."""
+    _chk(x, g, partials)
+    if partials.dtype != torch.float64 or (g is not None and g.numel() != x.numel()):
+        raise ValueError('reg_pass: float64 partials and a gradient of the size of x are expected')
+    _lib.call('gn_reg_pass', _p(x), _p(g), x.numel(), float(l1), float(l2), _p(partials), partials.numel(), _stream())
+
+
+def reg_grad(y, g, l1, l2, inplace=False):
+    """g + l1 sign(y) + 2 l2 y (the gradient of an activity penalty, added to the gradient arriving at y), into g itself or a new tensor."""
+    _chk(y, g)
+    if g.numel() != y.numel():
+        raise ValueError('reg_grad: a gradient of %d values for an output of %d' % (g.numel(), y.numel()))
+    out = g if inplace else torch.empty_like(g)
+    _lib.call('gn_reg_grad', _p(y), _p(g), _p(out), y.numel(), float(l1), float(l2), _stream())
+    return out
+
+
+def reg_finish(partials, out):
+    """out[0] (fp32) = the sum of all fp64 partials, in a fixed order, rounded once."""
+    _chk(partials, out)
+    _lib.call('gn_reg_finish', _p(partials), partials.numel(), _p(out), _stream())
+
+
 class DevScalar(object):
     """Address of one step-varying scalar in a step graph's parameter block (engine.StepGraph.slot)."""
 

@@ -471,6 +471,24 @@ size_t gn_optim_sumsq_slots(size_t n);
 int gn_optim_sumsq(const float* g, size_t n, double* partials, void* stream);
 int gn_optim_clip_factor(const double* partials, size_t count, float clipnorm, float* factor, void* stream);
 
+/* ---- Keras weight and activity regularizers (gennet_amd/csrc/regularizer.hip): regularizers.l1 / l2 / l1_l2 on a
+ * weight (kernel_regularizer, bias_regularizer, beta_, gamma_, alpha_) or on a layer's output (activity_regularizer, ActivityRegularization).
+ * The penalty of a tensor x of n floats is l1 * sum |x| + l2 * sum x^2, its gradient l1 * sign(x) + 2 * l2 * x with sign(+-0) = 0.
+ *   gn_reg_pass    reads x once; writes gn_reg_partials(n) fp64 block partials of the penalty (terms formed in fp64) to partials[0 ..) with
+ *                  plain stores and, with g != NULL, g[i] += l1 * sign(x[i]) + 2 * l2 * x[i] (fp32, three roundings).  g == NULL: penalty only
+ *                  (a frozen weight, the test phase), nothing but the partials is written.
+ *   gn_reg_grad    the gradient part alone (the activity backward): gout[i] = gin[i] + l1 * sign(y[i]) + 2 * l2 * y[i]; gout may be gin.
+ *   gn_reg_finish  one block: adds `count` partials -- those of every penalty of a step, side by side -- in a fixed order and writes one
+ *                  fp32 scalar, rounded once.
+ * No atomics: two runs give the same bits.  The launch shape and gn_reg_partials depend on n only.  Any 4-byte alignment: 16-byte loads and
+ * stores where the tensors of a pass share a 16-byte phase (a scalar head and tail around them), scalar ones otherwise.
+ * GN_EINVAL, nothing launched: a NULL pointer (except gn_reg_pass' g), n == 0 (count == 0), a negative or non-finite l1 / l2, n_partials <
+ * gn_reg_partials(n), partials not 8-byte aligned. */
+size_t gn_reg_partials(size_t n);
+int gn_reg_pass(const float* x, float* g, size_t n, float l1, float l2, double* partials, size_t n_partials, void* stream);
+int gn_reg_grad(const float* y, const float* gin, float* gout, size_t n, float l1, float l2, void* stream);
+int gn_reg_finish(const double* partials, size_t count, float* out, void* stream);
+
 /* ---- hipGraph capture of a whole train step (bbhMahoGANy.py:1153-1168, :1241-1299 at the script's own batch size 8, where the loop is
  * launch-bound): every launch of the library is stream-ordered and allocation-free, so train_on_batch can be captured on the launch stream and
  * replayed.  Scalars that change from step to step would be frozen into the graph as by-value kernel arguments; these entry points read them
