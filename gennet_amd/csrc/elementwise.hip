@@ -1,5 +1,6 @@
 // Streaming (HBM-bound) kernels and their entry points: activations, dropout, upsample, the two stack layers, the discriminator batch,
-// gather, axpy and the RNG fills.  All are grid-stride loops sized to ~8 blocks/CU, float4-vectorised where the layout allows.
+// gather, axpy and the RNG fills.  All are grid-stride loops sized to ~8 blocks/CU, float4-vectorised where the layout allows; UpSampling1D takes
+// any channel count and any 4-byte aligned base on one-float units (16-byte units only when C % 4 == 0 and both pointers are 16-byte aligned).
 #include "common.h"
 
 namespace gn {
@@ -85,23 +86,30 @@ __global__ void dropout_apply_kernel(const float* __restrict__ x, const uint8_t*
 // ---------------------------------------------------------------------------------------------
 // UpSampling1D(2), MyLayer stack, gather, axpy, RNG fills
 // ---------------------------------------------------------------------------------------------
-__global__ void upsample2_fwd_kernel(const float4* __restrict__ x, float4* __restrict__ y, size_t rows, int C4) {
-  const size_t n = rows * C4, stride = (size_t)gridDim.x * blockDim.x;
+// One lane owns one unit of the UN-upsampled tensor: a float4 when C % 4 == 0 and both tensors are 16-byte aligned, else one float (any channel
+// count, any 4-byte aligned base; as dilate.hip chooses).  C: units per row.
+__device__ __forceinline__ float add_unit(float a, float b) { return a + b; }
+__device__ __forceinline__ float4 add_unit(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+template <typename T>
+__global__ void upsample2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, size_t rows, int C) {
+  const size_t n = rows * C, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const size_t r = i / C4, c = i % C4;
-    const float4 v = x[i];
-    y[(2 * r) * C4 + c] = v;
-    y[(2 * r + 1) * C4 + c] = v;
+    const size_t r = i / C, c = i % C;
+    const T v = x[i];
+    y[(2 * r) * C + c] = v;
+    y[(2 * r + 1) * C + c] = v;
   }
 }
-__global__ void upsample2_bwd_kernel(const float4* __restrict__ dy, float4* __restrict__ dx, size_t rows, int C4) {
-  const size_t n = rows * C4, stride = (size_t)gridDim.x * blockDim.x;
+template <typename T>
+__global__ void upsample2_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, size_t rows, int C) {
+  const size_t n = rows * C, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const size_t r = i / C4, c = i % C4;
-    const float4 a = dy[(2 * r) * C4 + c], b = dy[(2 * r + 1) * C4 + c];
-    dx[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    const size_t r = i / C, c = i % C;
+    dx[i] = add_unit(dy[(2 * r) * C + c], dy[(2 * r + 1) * C + c]);
   }
 }
+static inline bool upsample2_vec(const void* a, const void* b, int C) { return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 __global__ void subtract_stack_fwd_kernel(const float* __restrict__ x, const float* __restrict__ ev, float2* __restrict__ img, size_t total, int n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -253,18 +261,24 @@ int gn_dropout_apply(const float* x, const uint8_t* mask, float* y, size_t n, fl
 
 int gn_upsample2_fwd(const float* x, float* y, int B, int L, int C, void* stream) {
   GN_REQUIRE(x && y, "upsample2_fwd: null pointer");
-  GN_REQUIRE(C % 4 == 0, "upsample2: C %d %% 4 != 0", C);
+  GN_REQUIRE(C >= 1, "upsample2: C %d < 1", C);
   const size_t rows = (size_t)B * L;
   if (!rows) return GN_OK;
-  hipLaunchKernelGGL(upsample2_fwd_kernel, dim3(stream_grid(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (float4*)y, rows, C / 4);
+  if (upsample2_vec(x, y, C))
+    hipLaunchKernelGGL(upsample2_fwd_kernel<float4>, dim3(stream_grid(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (float4*)y, rows, C / 4);
+  else
+    hipLaunchKernelGGL(upsample2_fwd_kernel<float>, dim3(stream_grid(rows * C)), dim3(256), 0, (hipStream_t)stream, x, y, rows, C);
   return check_launch("upsample2_fwd");
 }
 int gn_upsample2_bwd(const float* dy, float* dx, int B, int L, int C, void* stream) {
   GN_REQUIRE(dy && dx, "upsample2_bwd: null pointer");
-  GN_REQUIRE(C % 4 == 0, "upsample2: C %d %% 4 != 0", C);
+  GN_REQUIRE(C >= 1, "upsample2: C %d < 1", C);
   const size_t rows = (size_t)B * L;
   if (!rows) return GN_OK;
-  hipLaunchKernelGGL(upsample2_bwd_kernel, dim3(stream_grid(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (float4*)dx, rows, C / 4);
+  if (upsample2_vec(dy, dx, C))
+    hipLaunchKernelGGL(upsample2_bwd_kernel<float4>, dim3(stream_grid(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, (const float4*)dy, (float4*)dx, rows, C / 4);
+  else
+    hipLaunchKernelGGL(upsample2_bwd_kernel<float>, dim3(stream_grid(rows * C)), dim3(256), 0, (hipStream_t)stream, dy, dx, rows, C);
   return check_launch("upsample2_bwd");
 }
 

@@ -273,7 +273,7 @@ class Conv1D(Layer):
         """The planner (Model._plan) asks per instance: a channel pair that only the `anyc` kernels take has no fused Dropout, so the Dropout layer
         runs on its own.  Asked before an UpSampling1D fold is decided, so for every 5-tap 'same' layer neither the unfolded nor the folded pair
         may need them, folded or not in the end: declining costs one pass, fusing wrongly an error.
-        (For <= 4 filters that also turns the NotImplementedError of the fused Dropout into an unfused Dropout on such pairs, e.g. 8 -> 3.)"""
+        A built layer with <= 4 filters declines as well: its Dropout runs as a pass of its own."""
         if self.phased:              # the mask would be in the layer's layout, the conv's epilogue in the phase layout
             return False
         if _is_softmax(self):        # the conv's epilogue runs in front of the softmax pass, the Dropout behind it
@@ -281,6 +281,8 @@ class Conv1D(Layer):
         k = getattr(self, 'kernel', None)
         if k is None:
             return True
+        if self.filters <= 4:        # the small-Cout kernels have no Dropout epilogue (gn_conv1d_fwd_dropout needs more than 4 columns)
+            return False
         return not any(_ConvRun(self, k.shape[1], up).any_channels for up in ((False, True) if self.can_fold_upsample() else (False,)))
 
     def __init__(self, filters, kernel_size, strides=1, padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True,
@@ -441,9 +443,12 @@ class Conv2D(Layer):
 
     @property
     def fusable_drop(self):
-        return not _is_softmax(self)
+        """the launched conv has 2 * filters columns, and the fused Dropout epilogue needs more than 4 (gn_conv1d_fwd_dropout)"""
+        return not _is_softmax(self) and self.filters > 2
 
-    offers_act_bwd = fusable_drop
+    @property
+    def offers_act_bwd(self):
+        return not _is_softmax(self)
 
     def __init__(self, filters, kernel_size, strides=(1, 1), padding='valid', activation=None, kernel_initializer='glorot_uniform', use_bias=True,
                  kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, **kw):
@@ -462,6 +467,11 @@ class Conv2D(Layer):
         H, W, Cin = input_shape
         if W != 2:
             raise NotImplementedError('Conv2D is implemented for width-2 images (got width %d)' % W)
+        if ops.conv_layer_needs_any(2 * Cin, 2 * self.filters):
+            # the layer runs as a Conv1D over (w, c)-interleaved rows, 2 * Cin -> 2 * filters, on the strict entry points
+            raise NotImplementedError('Conv2D(%d filters) on %d input channels: the width-2 layer runs as a %d -> %d channel Conv1D, and the conv '
+                                      'kernels it uses need both counts multiples of 4, or one of them <= 4 and the other a multiple of 4'
+                                      % (self.filters, Cin, 2 * Cin, 2 * self.filters))
         self.kernel = self.add_weight('kernel', glorot_uniform((self.kh, self.kw, Cin, self.filters)), regularizer=self.kernel_regularizer)
         self.bias = self.add_weight('bias', np.zeros(self.filters, np.float32), regularizer=self.bias_regularizer)
 
@@ -1315,6 +1325,10 @@ class MyLayer(Layer):
         Layer.__init__(self, **kw)
         self._const_host = np.asarray(const, np.float32).reshape(-1)
         self._const = None
+
+    def get_const(self):
+        """the layer's constant as the host array it was given (float32, flat)"""
+        return self._const_host.copy()
 
     @property
     def const(self):

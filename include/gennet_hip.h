@@ -85,7 +85,8 @@ int gn_conv1d_fwd_stats(const float* x, const float* w, const float* bias, float
 int gn_conv1d_transpose_w(const float* w, float* wt, int k, int Cin, int Cout, void* stream);
 
 /* dx[b,tau,ci] = sum_{k,co} dy[b,t,co] * w[k,ci,co] over stride*t + k - pad_left == tau.  wt from
- * gn_conv1d_transpose_w.  (Backward of the call sites above; TF Conv2DBackpropInput.) */
+ * gn_conv1d_transpose_w.  (Backward of the call sites above; TF Conv2DBackpropInput.)  k < stride: the rows tau no tap reaches are written
+ * as zeros (dx is cleared first, then the phases that have taps run). */
 int gn_conv1d_dgrad(const float* dy, const float* wt, float* dx,
                     int B, int L, int Cin, int Cout, int k, int stride, int pad_left, int Lout, void* stream);
 
@@ -200,7 +201,8 @@ int gn_prelu_bwd(const float* dy, const float* x, const float* alpha, float* dx,
  * element i draws counter (offset + i/4), lane i%4; keep iff u >= rate) and application y = x*mask/(1-rate). */
 int gn_dropout_mask(uint8_t* mask, size_t n, float rate, uint64_t seed, uint64_t offset, void* stream);
 int gn_dropout_apply(const float* x, const uint8_t* mask, float* y, size_t n, float rate, void* stream);
-/* UpSampling1D(size=2) (bbhMahoGANy.py:249,:258) and its adjoint */
+/* UpSampling1D(size=2) (bbhMahoGANy.py:249,:258) and its adjoint: x (B, L, C) -> y (B, 2L, C), every row twice; dx = the sum of the two rows.
+ * Any C >= 1: float4 units when C % 4 == 0 and both base pointers are 16-byte aligned, else floats. */
 int gn_upsample2_fwd(const float* x, float* y, int B, int L, int C, void* stream);
 int gn_upsample2_bwd(const float* dy, float* dx, int B, int L, int C, void* stream);
 /* MaxPooling2D(pool_size=(2,1)) (the discriminator's `maxpool = True` configuration, bbhMahoGANy.py:426, :444-490): x (B, H, R) -> y (B, H/2, R), the

@@ -56,8 +56,8 @@ CASES = [
     ('gn_act_dropout_bwd', [P, P, P, P, 0, 1, 0.0, 0.5, None]),
     ('gn_dropout_mask', [None, 8, 0.5, 1, 0, None]), ('gn_dropout_mask', [P, 8, -0.25, 1, 0, None]), ('gn_dropout_mask', [P, 0, 0.5, 1, 0, None]),
     ('gn_dropout_apply', [P, None, P, 8, 0.5, None]), ('gn_dropout_apply', [P, P, P, 8, 1.0, None]), ('gn_dropout_apply', [P, P, P, 0, 0.5, None]),
-    ('gn_upsample2_fwd', [None, P, 2, 8, 8, None]), ('gn_upsample2_fwd', [P, P, 2, 8, 6, None]), ('gn_upsample2_fwd', [P, P, 0, 8, 8, None]),
-    ('gn_upsample2_bwd', [P, None, 2, 8, 8, None]), ('gn_upsample2_bwd', [P, P, 2, 8, 6, None]), ('gn_upsample2_bwd', [P, P, 2, 0, 8, None]),
+    ('gn_upsample2_fwd', [None, P, 2, 8, 8, None]), ('gn_upsample2_fwd', [P, P, 2, 8, 0, None]), ('gn_upsample2_fwd', [P, P, 0, 8, 8, None]),
+    ('gn_upsample2_bwd', [P, None, 2, 8, 8, None]), ('gn_upsample2_bwd', [P, P, 2, 8, 0, None]), ('gn_upsample2_bwd', [P, P, 2, 0, 8, None]),
     ('gn_subtract_stack_fwd', [P, None, P, 2, 8, None]), ('gn_subtract_stack_fwd', [P, P, P, 0, 8, None]),
     ('gn_subtract_stack_bwd', [None, P, 2, 8, None]), ('gn_subtract_stack_bwd', [P, P, 2, 0, None]),
     ('gn_affine_stack_fwd', [None, P, P, 1.0, -1.0, P, 2, 8, None]), ('gn_affine_stack_fwd', [P, None, None, 1.0, -1.0, P, 2, 0, None]),
