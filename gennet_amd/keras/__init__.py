@@ -10,7 +10,7 @@
     from gennet_amd.keras import regularizers                          # l1, l2, l1_l2, L1L2, get, serialize, deserialize
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
-    from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, add, concatenate, ...                # all seven merge layers and functions
+    from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, Dot, add, dot, ...                   # all eight merge layers and functions
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -67,8 +67,8 @@ _pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'A
                  'GlobalMaxPooling1D', 'GlobalMaxPooling2D')
 _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU', 'Softmax'), **_unused('39', 'ThresholdedReLU'))
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
-_merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate',
-               'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate')
+_merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate', 'Dot',
+               'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))

@@ -228,6 +228,8 @@ def layer_config(layer):
         cfg.update(data_format='channels_last')
     elif isinstance(layer, L.Concatenate):       # keras 2.2.4 layers/merge.py: the six element-wise layers write the base config only
         cfg.update(axis=layer.axis)
+    elif isinstance(layer, L.Dot):               # axes as keras writes it: the int, or the pair as a list
+        cfg.update(axes=layer.axes if isinstance(layer.axes, int) else list(layer.axes), normalize=layer.normalize)
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -346,6 +348,8 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return getattr(L, class_name)(**kw)
     if class_name == 'Concatenate':
         return L.Concatenate(axis=cfg.get('axis', -1), **kw)
+    if class_name == 'Dot':
+        return L.Dot(axes=cfg['axes'], normalize=cfg.get('normalize', False), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 

@@ -1500,3 +1500,7 @@ def minimum(inputs, **kw):
 
 def concatenate(inputs, axis=-1, **kw):
     return Concatenate(axis=axis, **kw)(inputs)
+
+
+# keras.layers.Dot / dot live in gennet_amd/dot.py and are part of this name space
+from .dot import Dot, dot  # noqa: E402,F401

@@ -489,6 +489,55 @@ def softmax_bwd(dy, y, view, out=None, inplace=False):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- batched product, l2 normalisation (csrc/bmm.hip)
+def bmm(a, b, trans_a=False, trans_b=False, out=None, valu=False):
+    """c (batch, M, N) = A . B per batch entry over contiguous 3-D tensors: A = a (batch, M, K), or a^T of a (batch, K, M) under trans_a;
+    B = b (batch, K, N), or b^T of b (batch, N, K) under trans_b.  Nothing is transposed in memory: the flags only choose the strides.
+    valu=True runs gn_bmm_valu, the 16 x 16 VALU tile (the yardstick of scripts/bmm_microbench.py; the same bits)."""
+    _chk(a, b, out)
+    if a.dim() != 3 or b.dim() != 3 or a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape[0] != b.shape[0]:
+        raise ValueError('bmm: float32 tensors (batch, ., .) of one batch size are expected, got %r and %r' % (tuple(a.shape), tuple(b.shape)))
+    batch = a.shape[0]
+    K, M = (a.shape[1], a.shape[2]) if trans_a else (a.shape[2], a.shape[1])
+    Kb, N = (b.shape[2], b.shape[1]) if trans_b else (b.shape[1], b.shape[2])
+    if K != Kb:
+        raise ValueError('bmm: the contracted extents differ, %d and %d (a %r%s, b %r%s)'
+                         % (K, Kb, tuple(a.shape), '^T' if trans_a else '', tuple(b.shape), '^T' if trans_b else ''))
+    c = torch.empty((batch, M, N), dtype=torch.float32, device=a.device) if out is None else out
+    assert c.numel() == batch * M * N
+    a_m, a_k = (1, M) if trans_a else (K, 1)
+    b_k, b_n = (1, K) if trans_b else (N, 1)
+    _lib.call('gn_bmm_valu' if valu else 'gn_bmm', _p(a), _p(b), _p(c), batch, M, N, K, M * K, a_m, a_k, K * N, b_k, b_n, _stream())
+    return c
+
+
+def _l2norm_view(t, view):
+    outer, P, inner = (int(v) for v in view)
+    if outer < 0 or P < 1 or inner < 1 or outer * P * inner != t.numel():
+        raise ValueError('l2norm: the (outer, P, inner) view %r does not cover a tensor of %d elements' % ((outer, P, inner), t.numel()))
+    return outer, P, inner
+
+
+def l2norm_fwd(x, view):
+    """(y, inv): y = x * inv along the middle axis of the (outer, P, inner) view, inv (outer, inner) = 1 / sqrt(max(sum_p x^2, 1e-12)) (tf.nn.l2_normalize)"""
+    _chk(x)
+    outer, P, inner = _l2norm_view(x, view)
+    y = torch.empty_like(x)
+    inv = torch.empty((outer, inner), dtype=torch.float32, device=x.device)
+    _lib.call('gn_l2norm_fwd', _p(x), _p(y), _p(inv), outer, P, inner, _stream())
+    return y, inv
+
+
+def l2norm_bwd(dy, y, inv, view, out=None):
+    """dx = inv * (dy - y * sum_p dy * y) from the stored y and inv; inv * dy where the sum of squares was clamped"""
+    _chk(dy, y, inv, out)
+    outer, P, inner = _l2norm_view(dy, view)
+    assert y.numel() == dy.numel() and inv.numel() == outer * inner
+    dx = torch.empty_like(dy) if out is None else out
+    _lib.call('gn_l2norm_bwd', _p(dy), _p(y), _p(inv), _p(dx), outer, P, inner, _stream())
+    return dx
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

@@ -399,6 +399,30 @@ int gn_bn_axis_bwd_apply(const float* dy, const float* x, const float* gamma, co
 int gn_softmax_fwd(const float* x, float* y, size_t outer, int P, int inner, void* stream);
 int gn_softmax_bwd(const float* dy, const float* y, float* dx, size_t outer, int P, int inner, void* stream);
 
+/* ---- batched fp32 matrix product (csrc/bmm.hip; keras layers.Dot through K.batch_dot):
+ *   c[(bt*M + m)*N + n] = sum_k a[bt*a_batch + m*a_m + k*a_k] * b[bt*b_batch + k*b_k + n*b_n]      strides in elements, c contiguous.
+ * For each operand one of its two matrix strides is 1 and the other at least the extent of the contiguous axis, so the product, a . b^T,
+ * a^T . b and a^T . b^T are this one call and Dot's gradients land in their owner's layout.  M, N >= 2 run on the fp32 matrix cores
+ * (v_mfma_f32_32x32x2_f32, block tiles of 64 or 128 per side, K in chunks of 16 through LDS, 16-byte loads along the unit stride where the base
+ * pointer is 16-byte aligned and the batch stride and row length are multiples of 4, scalar loads otherwise); M == 1 or N == 1 on a
+ * matrix-vector kernel (a wave per output when the matrix rows are contiguous in k, else a lane per output).  No split-K, no atomics, no
+ * workspace: on the matrix cores every output is one fp32 fma chain in k order from +0, so it does not depend on the tile, the batch or
+ * the launch; the wave-per-output sum has a fixed order that depends on K alone.  gn_bmm_valu is the same contract on a 16 x 16 VALU tile
+ * (one fmaf chain per lane: the same bits as the matrix-core kernel), kept as the yardstick of scripts/bmm_microbench.py; nothing selects it.
+ * GN_EINVAL, nothing launched: a negative size, K < 1, a stride <= 0, a stride pair that is not {1, >= extent}, a NULL pointer with
+ * non-zero work, more than 2^31 - 1 blocks, an operand spanning 2^62 elements.  batch == 0, M == 0 or N == 0 is GN_OK without a launch. */
+int gn_bmm(const float* a, const float* b, float* c, int batch, int M, int N, int K, long long a_batch, long long a_m, long long a_k,
+           long long b_batch, long long b_k, long long b_n, void* stream);
+int gn_bmm_valu(const float* a, const float* b, float* c, int batch, int M, int N, int K, long long a_batch, long long a_m, long long a_k,
+                long long b_batch, long long b_k, long long b_n, void* stream);
+
+/* ---- L2 normalisation along one axis (csrc/bmm.hip; Dot(normalize=True): K.l2_normalize = tf.nn.l2_normalize) on the (outer, P, inner) view:
+ *   s = sum_p x^2, inv[(o, i)] = 1 / sqrt(max(s, 1e-12)), y = x * inv;  dx = inv * (dy - y * sum_p dy * y), and dx = inv * dy where s was
+ *   clamped (inv is then exactly 1e6f, which is how the backward tells).  inv holds outer * inner floats.  fp32 sums in a fixed order, no atomics.
+ * GN_EINVAL, nothing launched: a NULL pointer, P / inner < 1, P * inner >= 2^31, outer * P * inner >= 2^62.  outer == 0 is GN_OK. */
+int gn_l2norm_fwd(const float* x, float* y, float* inv, size_t outer, int P, int inner, void* stream);
+int gn_l2norm_bwd(const float* dy, const float* y, const float* inv, float* dx, size_t outer, int P, int inner, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
