@@ -1,0 +1,408 @@
+// keras.layers.LSTM (keras 2.2.4 layers/recurrent.py, LSTMCell): the recurrence as one persistent kernel a direction; DESIGN 8o.
+//
+//   z_t = zx_t + h_{t-1} . U + b        zx = X . W for all steps comes in (one gn_bmm over B T rows), gate columns i, f, c, o of width u
+//   i = ra(z_i)  f = ra(z_f)  g = act(z_c)  o = ra(z_o)        c_t = f c_{t-1} + i g        h_t = o act(c_t)
+//
+// OWNERSHIP.  The recurrence couples the units of one sample and never two samples, so a block owns LSTM_ROWS = 16 batch rows and walks all T
+// steps alone: no block waits on another one, no grid barrier, no cooperative launch, no atomics.  grid = ceil(B / 16) blocks.
+//
+// TILING.  The step product (16, u) x (u, 4u) runs on v_mfma_f32_16x16x4_f32 (A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15],
+// C[row = 4 (lane >> 4) + reg][col = lane & 15]).  A wave owns NT tiles of 16 units (tile = wave + nwaves i) and forms the FOUR gate columns of its
+// units in four accumulators, so a lane holds z_i, z_f, z_c, z_o of the same (row, unit) and the gate arithmetic, c_t and h_t never leave its
+// registers; c lives in registers for the whole sequence (4 NT a lane).  h lies in LDS as hs[row][k] with a row of KP + 1 floats (KP = u up to a
+// multiple of 8; odd row length: the 16 rows of a fragment read fall on 16 banks), twice: step t reads one copy and writes the other, ONE barrier a
+// step.  nwaves = ceil(ntiles / NT) <= 8, NT = ceil(ntiles / 8) <= 4 (lstm_geom.h).
+//   backward: the same ownership, t walks down.  A lane holds dh and dc of its (row, unit) in registers, forms the four dz of the step from the
+// stored gates and c, writes them to global memory and to LDS (dzs[row][gate KP + k], a row of 4 KP + 1 floats), and after a barrier the wave forms
+// dh_{t-1} = dz_t . U^T for its units as one chain over the 4 KP gate columns; a second barrier frees dzs for the next step.
+//
+// U.  The entry points first write a zero-padded copy of U into the workspace (one small launch): forward Up[k][gate UP + j] with a row of
+// SU = 4 UP + 16 floats, backward the transpose Ut[gate KP + k][j] with a row of SUT = UP | 16 floats (UP = u up to a multiple of 16), so the
+// B fragments are 16 consecutive floats a k row, no guard stands in the loops, and everything outside u is an exact +0.  Which path a u takes is
+// decided in ONE place, lstm_geom():
+//   forward   u <= 88: the padded U is copied into LDS once a block (the state and U fit 160 KiB);  89 <= u <= 512: U streams from L2 every step
+//   backward  u <= 80: U^T in LDS;  81 <= u <= 512: streamed
+//
+// NUMERICS.  Every z is ONE fp32 fma chain over k = 0 .. u-1 from +0 (the f32 MFMA is bit for bit that chain), then + zx, then + b; dh_{t-1} one chain
+// over the gate columns i, f, c, o in k order, then dy_{t-1} + that.  The padding adds fma(+0, +0, c) = c.  Row m of an MFMA result depends on row m of
+// A alone, so a sample's outputs and gradients do not depend on B, on the tile it falls in or on the launch; rows of a tile beyond B run on zeros and
+// are never stored.  tanh and sigmoid are gn_tanhf and the sigmoid of common.h; hard_sigmoid is min(max(0.2 x + 0.5, 0), 1) with the product and
+// the sum rounded separately, its derivative 0.2 where the stored gate is strictly between 0 and 1.
+//
+// STORED for the backward (training flag): the activated gates (B, T, 4u) and c (B, T, u) at the INPUT time index of their step, and hprev (B, T, u):
+// the h that entered the step at that input time (h0 at the first one).  With them dz lands at the input time index as well, so dW = X^T dz,
+// dU = hprev^T dz and dX = dz W^T are one product each over B T rows whatever the direction.  h itself is written in processing order, as keras
+// returns it.
+#include <math.h>
+
+#include "common.h"
+#include "lstm_geom.h"
+
+namespace gn {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float lstm_sigmoid(float x) { return act_apply(x, GN_ACT_SIGMOID, 0.f); }
+
+__device__ __forceinline__ float lstm_act(float x, int code) {
+  switch (code) {
+    case GN_LSTM_TANH: return gn_tanhf(x);
+    case GN_LSTM_SIGMOID: return lstm_sigmoid(x);
+    case GN_LSTM_RELU: return fmaxf(x, 0.f);
+    case GN_LSTM_HARD_SIGMOID: return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
+    default: return x;
+  }
+}
+
+// the derivative through the OUTPUT value y = act(x)
+__device__ __forceinline__ float lstm_act_grad(float y, int code) {
+  switch (code) {
+    case GN_LSTM_TANH: return 1.f - y * y;
+    case GN_LSTM_SIGMOID: return y * (1.f - y);
+    case GN_LSTM_RELU: return y > 0.f ? 1.f : 0.f;
+    case GN_LSTM_HARD_SIGMOID: return (y > 0.f && y < 1.f) ? 0.2f : 0.f;
+    default: return 1.f;
+  }
+}
+
+struct LstmFwdArgs {
+  const float* zx;      // (B, T, 4u)
+  const float* up;      // padded U: KP rows of SU floats
+  const float* bias;    // (4u)
+  const float* h0;      // (B, u) or NULL
+  const float* c0;
+  float* h;             // (B, T, u), processing order
+  float* gates;         // (B, T, 4u), input time order; training only
+  float* c;             // (B, T, u)
+  float* hprev;         // (B, T, u)
+  int B, T, u, KP, UP, SU, ntiles, act, ract, reverse, training;
+};
+
+template <int NT, bool ULDS>
+__global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lstm_lds[];
+  const int SH = g.KP + 1;
+  float* hs0 = lstm_lds;
+  float* hs1 = lstm_lds + LSTM_ROWS * SH;
+  float* us = lstm_lds + 2 * LSTM_ROWS * SH;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int fc = lane & 15, fq = lane >> 4;
+  const size_t b0 = (size_t)blockIdx.x * LSTM_ROWS;
+  const size_t u = (size_t)g.u, T = (size_t)g.T;
+
+  for (int e = threadIdx.x; e < LSTM_ROWS * SH; e += blockDim.x) {
+    const int row = e / SH, k = e % SH;
+    hs0[e] = (g.h0 && k < g.u && b0 + row < (size_t)g.B) ? g.h0[(b0 + row) * u + k] : 0.f;
+    hs1[e] = 0.f;
+  }
+  if (ULDS)
+    for (int e = threadIdx.x; e < g.KP * g.SU; e += blockDim.x) us[e] = g.up[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : g.up;
+
+  float creg[NT][4], bias[NT][4];
+  const size_t t_first = g.reverse ? T - 1 : 0;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
+    const bool jok = tile < g.ntiles && j < g.u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bias[i][q] = jok ? g.bias[q * g.u + j] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const size_t row = b0 + 4 * fq + r;
+      const bool ok = jok && row < (size_t)g.B;
+      creg[i][r] = (ok && g.c0) ? g.c0[row * u + j] : 0.f;
+      if (ok && g.training) g.hprev[(row * T + t_first) * u + j] = g.h0 ? g.h0[row * u + j] : 0.f;
+    }
+  }
+  __syncthreads();
+
+  for (int s = 0; s < g.T; ++s) {
+    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
+    const size_t t_next = g.reverse ? t_in - 1 : t_in + 1;          // read only while s + 1 < T
+    const float* cur = (s & 1) ? hs1 : hs0;
+    float* nxt = (s & 1) ? hs0 : hs1;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int tile = wave + nw * i;
+      if (tile < g.ntiles) {                                        // the same for all lanes of a wave
+        const int j0 = tile * LSTM_TILE, j = j0 + fc;
+        const bool jok = j < g.u;
+        float zv[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const size_t row = b0 + 4 * fq + r;
+          const bool ok = jok && row < (size_t)g.B;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) zv[q][r] = ok ? g.zx[((row * T + t_in) * 4 + q) * u + j] : 0.f;
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* ap = cur + fc * SH + fq;
+        const float* bp = ub + fq * g.SU + j;
+        for (int k0 = 0; k0 < g.KP; k0 += 8) {                       // KP is a multiple of 8: two k groups of 4 a turn, loads first
+          const float* bk = bp + (size_t)k0 * g.SU;
+          float a[2], b[2][4];
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk) {
+            a[kk] = ap[k0 + 4 * kk];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[kk][q] = bk[(size_t)4 * kk * g.SU + q * g.UP];
+          }
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b[kk][q], acc[q], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const size_t row = b0 + 4 * fq + r;
+          const float gi = lstm_act((acc[0][r] + zv[0][r]) + bias[i][0], g.ract);
+          const float gf = lstm_act((acc[1][r] + zv[1][r]) + bias[i][1], g.ract);
+          const float gg = lstm_act((acc[2][r] + zv[2][r]) + bias[i][2], g.act);
+          const float go = lstm_act((acc[3][r] + zv[3][r]) + bias[i][3], g.ract);
+          const float cn = gf * creg[i][r] + gi * gg;
+          const float hn = go * lstm_act(cn, g.act);
+          creg[i][r] = cn;
+          if (jok) {
+            nxt[(4 * fq + r) * SH + j] = hn;
+            if (row < (size_t)g.B) {
+              g.h[(row * T + s) * u + j] = hn;
+              if (g.training) {
+                float* gp = g.gates + (row * T + t_in) * 4 * u + j;
+                gp[0] = gi;
+                gp[u] = gf;
+                gp[2 * u] = gg;
+                gp[3 * u] = go;
+                g.c[(row * T + t_in) * u + j] = cn;
+                if (s + 1 < g.T) g.hprev[(row * T + t_next) * u + j] = hn;
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();          // h_t is complete in nxt, and every wave has left cur, which step t + 1 overwrites
+  }
+}
+
+struct LstmBwdArgs {
+  const float* dy;      // (B, T, u) in processing order, or (B, u) for the last step
+  const float* gates;
+  const float* c;
+  const float* c0;
+  const float* utp;     // padded U^T: 4 KP rows of SUT floats
+  float* dz;            // (B, T, 4u), input time order
+  float* dh0;           // (B, u) or NULL
+  float* dc0;
+  int B, T, u, KP, UP, SUT, ntiles, act, ract, reverse, dy_seq;
+};
+
+template <int NT, bool ULDS>
+__global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lstm_lds[];
+  const int SD = 4 * g.KP + 1;
+  float* dzs = lstm_lds;
+  float* us = lstm_lds + LSTM_ROWS * SD;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int fc = lane & 15, fq = lane >> 4;
+  const size_t b0 = (size_t)blockIdx.x * LSTM_ROWS;
+  const size_t u = (size_t)g.u, T = (size_t)g.T;
+
+  for (int e = threadIdx.x; e < LSTM_ROWS * SD; e += blockDim.x) dzs[e] = 0.f;
+  if (ULDS)
+    for (int e = threadIdx.x; e < 4 * g.KP * g.SUT; e += blockDim.x) us[e] = g.utp[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : g.utp;
+
+  float dh[NT][4], dc[NT][4];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dh[i][r] = dc[i][r] = 0.f;
+  __syncthreads();
+
+  for (int s = g.T - 1; s >= 0; --s) {
+    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
+    const size_t t_prev = g.reverse ? t_in + 1 : t_in - 1;          // read only while s > 0
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
+      if (tile < g.ntiles && j < g.u) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const size_t row = b0 + 4 * fq + r;
+          if (row < (size_t)g.B) {                                  // rows beyond B keep their +0 in dzs
+            const float* gp = g.gates + (row * T + t_in) * 4 * u + j;
+            const float gi = gp[0], gf = gp[u], gg = gp[2 * u], go = gp[3 * u];
+            const float cs = g.c[(row * T + t_in) * u + j];
+            const float cp = s > 0 ? g.c[(row * T + t_prev) * u + j] : (g.c0 ? g.c0[row * u + j] : 0.f);
+            const float dyv = g.dy_seq ? g.dy[(row * T + s) * u + j] : (s == g.T - 1 ? g.dy[row * u + j] : 0.f);
+            const float dhv = dyv + dh[i][r];
+            const float tc = lstm_act(cs, g.act);
+            const float dcv = dc[i][r] + (dhv * go) * lstm_act_grad(tc, g.act);
+            const float dzi = (dcv * gg) * lstm_act_grad(gi, g.ract);
+            const float dzf = (dcv * cp) * lstm_act_grad(gf, g.ract);
+            const float dzg = (dcv * gi) * lstm_act_grad(gg, g.act);
+            const float dzo = (dhv * tc) * lstm_act_grad(go, g.ract);
+            dc[i][r] = dcv * gf;
+            float* zp = g.dz + (row * T + t_in) * 4 * u + j;
+            zp[0] = dzi;
+            zp[u] = dzf;
+            zp[2 * u] = dzg;
+            zp[3 * u] = dzo;
+            float* ls = dzs + (4 * fq + r) * SD + j;
+            ls[0] = dzi;
+            ls[g.KP] = dzf;
+            ls[2 * g.KP] = dzg;
+            ls[3 * g.KP] = dzo;
+          }
+        }
+      }
+    }
+    __syncthreads();          // dz_t is complete in dzs
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+      const int tile = wave + nw * i;
+      if (tile < g.ntiles) {
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* ap = dzs + fc * SD + fq;
+        const float* bp = ub + fq * g.SUT + tile * LSTM_TILE + fc;
+        for (int k0 = 0; k0 < 4 * g.KP; k0 += 32) {                  // 4 KP is a multiple of 32: eight k groups of 4 a turn, loads first
+          float a[8], b[8];
+#pragma unroll
+          for (int kk = 0; kk < 8; ++kk) {
+            a[kk] = ap[k0 + 4 * kk];
+            b[kk] = bp[(size_t)(k0 + 4 * kk) * g.SUT];
+          }
+#pragma unroll
+          for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b[kk], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dh[i][r] = acc[r];
+      }
+    }
+    __syncthreads();          // every wave has left dzs, which step t - 1 overwrites
+  }
+
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
+    if (tile < g.ntiles && j < g.u) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const size_t row = b0 + 4 * fq + r;
+        if (row < (size_t)g.B) {
+          if (g.dh0) g.dh0[row * u + j] = dh[i][r];
+          if (g.dc0) g.dc0[row * u + j] = dc[i][r];
+        }
+      }
+    }
+  }
+}
+
+// up[k * SU + q * UP + j] = U[k][q u + j], +0 outside u
+__global__ __launch_bounds__(256) void lstm_pad_u_kernel(const float* __restrict__ U, float* __restrict__ up, int u, int KP, int UP, int SU) {
+  const int n = KP * SU;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+    const int k = e / SU, col = e % SU, q = col / UP, j = col % UP;
+    up[e] = (k < u && q < 4 && j < u) ? U[(size_t)k * 4 * u + q * u + j] : 0.f;
+  }
+}
+
+// utp[(q * KP + k) * SUT + j] = U[j][q u + k], +0 outside u
+__global__ __launch_bounds__(256) void lstm_pad_ut_kernel(const float* __restrict__ U, float* __restrict__ utp, int u, int KP, int SUT) {
+  const int n = 4 * KP * SUT;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+    const int row = e / SUT, j = e % SUT, q = row / KP, k = row % KP;
+    utp[e] = (k < u && j < u) ? U[(size_t)j * 4 * u + q * u + k] : 0.f;
+  }
+}
+
+template <int NT, bool ULDS>
+void launch_fwd(const LstmFwdArgs& a, const LstmGeom& m, hipStream_t s) {
+  static unsigned long long big = 0;
+  allow_big_lds((const void*)lstm_fwd_kernel<NT, ULDS>, &big);
+  hipLaunchKernelGGL((lstm_fwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.fwd_lds_bytes, s, a);
+}
+
+template <int NT, bool ULDS>
+void launch_bwd(const LstmBwdArgs& a, const LstmGeom& m, hipStream_t s) {
+  static unsigned long long big = 0;
+  allow_big_lds((const void*)lstm_bwd_kernel<NT, ULDS>, &big);
+  hipLaunchKernelGGL((lstm_bwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
+}
+
+bool lstm_code_ok(int code, bool recurrent) {
+  return recurrent ? (code == GN_LSTM_HARD_SIGMOID || code == GN_LSTM_SIGMOID)
+                   : (code == GN_LSTM_TANH || code == GN_LSTM_SIGMOID || code == GN_LSTM_RELU || code == GN_LSTM_LINEAR);
+}
+
+// 0: launch, 1: nothing to do, GN_EINVAL: refused
+int lstm_check(const char* what, int B, int T, int u, int act, int ract) {
+  GN_REQUIRE(B >= 0 && T >= 1 && u >= 1, "%s: bad shape (B %d, T %d, u %d): B >= 0, T >= 1, u >= 1", what, B, T, u);
+  GN_REQUIRE(u <= LSTM_MAX_U, "%s: u = %d, at most %d units run (a block carries all units of its samples on chip)", what, u, LSTM_MAX_U);
+  GN_REQUIRE(lstm_code_ok(act, false), "%s: unknown activation code %d (GN_LSTM_TANH, _SIGMOID, _RELU, _LINEAR)", what, act);
+  GN_REQUIRE(lstm_code_ok(ract, true), "%s: unknown recurrent activation code %d (GN_LSTM_HARD_SIGMOID, GN_LSTM_SIGMOID)", what, ract);
+  GN_REQUIRE((unsigned long long)B * (unsigned long long)T < (1ull << 62) / (4ull * LSTM_MAX_U), "%s: B * T * 4u spans 2^62 elements or more", what);
+  return B == 0 ? 1 : 0;
+}
+
+}  // namespace
+}  // namespace gn
+
+using namespace gn;
+
+extern "C" {
+
+size_t gn_lstm_fwd_workspace(int u) { return (u < 1 || u > LSTM_MAX_U) ? 0 : lstm_geom(u).fwd_ws_floats * sizeof(float); }
+
+size_t gn_lstm_bwd_workspace(int u) { return (u < 1 || u > LSTM_MAX_U) ? 0 : lstm_geom(u).bwd_ws_floats * sizeof(float); }
+
+int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float* h0, const float* c0, float* h, float* gates, float* c, float* hprev,
+                void* ws, size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int training, void* stream) {
+  const int rc = lstm_check("lstm_fwd", B, T, u, act, ract);
+  if (rc) return rc < 0 ? rc : GN_OK;
+  GN_REQUIRE(zx && U && bias && h && ws, "lstm_fwd: null pointer (zx, U, bias, h and the workspace are required)");
+  GN_REQUIRE(!training || (gates && c && hprev), "lstm_fwd: null pointer (the training phase stores gates, c and hprev)");
+  const LstmGeom m = lstm_geom(u);
+  if (ws_bytes < m.fwd_ws_floats * sizeof(float)) {
+    set_error("lstm_fwd: workspace too small (%zu bytes, gn_lstm_fwd_workspace(%d) = %zu)", ws_bytes, u, m.fwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* up = (float*)ws;
+  hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U, up, u, m.KP, m.UP, m.SU);
+  const LstmFwdArgs a = {zx, up, bias, h0, c0, h, gates, c, hprev, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0};
+  if (m.fwd_u_lds) launch_fwd<1, true>(a, m, s);           // u <= 88: six tiles at the most, one a wave
+  else if (m.NT == 1) launch_fwd<1, false>(a, m, s);
+  else if (m.NT == 2) launch_fwd<2, false>(a, m, s);
+  else if (m.NT == 3) launch_fwd<3, false>(a, m, s);
+  else launch_fwd<4, false>(a, m, s);
+  return check_launch("lstm_fwd");
+}
+
+int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float* c0, const float* U, float* dz, float* dh0, float* dc0, void* ws,
+                size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int dy_seq, void* stream) {
+  const int rc = lstm_check("lstm_bwd", B, T, u, act, ract);
+  if (rc) return rc < 0 ? rc : GN_OK;
+  GN_REQUIRE(dy && gates && c && U && dz && ws, "lstm_bwd: null pointer (dy, gates, c, U, dz and the workspace are required)");
+  const LstmGeom m = lstm_geom(u);
+  if (ws_bytes < m.bwd_ws_floats * sizeof(float)) {
+    set_error("lstm_bwd: workspace too small (%zu bytes, gn_lstm_bwd_workspace(%d) = %zu)", ws_bytes, u, m.bwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* utp = (float*)ws;
+  hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U, utp, u, m.KP, m.SUT);
+  const LstmBwdArgs a = {dy, gates, c, c0, utp, dz, dh0, dc0, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0};
+  if (m.bwd_u_lds) launch_bwd<1, true>(a, m, s);           // u <= 80: five tiles at the most, one a wave
+  else if (m.NT == 1) launch_bwd<1, false>(a, m, s);
+  else if (m.NT == 2) launch_bwd<2, false>(a, m, s);
+  else if (m.NT == 3) launch_bwd<3, false>(a, m, s);
+  else launch_bwd<4, false>(a, m, s);
+  return check_launch("lstm_bwd");
+}
+
+}  // extern "C"

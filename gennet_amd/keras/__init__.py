@@ -11,6 +11,7 @@
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, Dot, add, dot, ...                   # all eight merge layers and functions
+    from gennet_amd.keras.layers.recurrent import LSTM                 # also gennet_amd.keras.layers.LSTM
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -69,10 +70,11 @@ _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU', 'Softmax'), **_unused('
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate', 'Dot',
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
+_recurrent = _pick(_layers, 'LSTM')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))
-for _d in (_core, _norm, _conv, _act, _noise, _merge):
+for _d in (_core, _norm, _conv, _act, _noise, _merge, _recurrent):
     _top.update((k, v) for k, v in _d.items() if v is _layers.__dict__.get(k))
 
 _TREE = {
@@ -90,6 +92,7 @@ _TREE = {
     'layers.noise': _noise,
     'layers.pooling': _pooling,
     'layers.merge': _merge,
+    'layers.recurrent': _recurrent,
     'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
     'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }

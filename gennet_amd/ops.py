@@ -538,6 +538,51 @@ def l2norm_bwd(dy, y, inv, view, out=None):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- LSTM recurrence (csrc/lstm.hip)
+LSTM_ACT = _lib.enum_members('GN_LSTM_')                        # enum gn_lstm_act: {'tanh': 0, 'sigmoid': 1, 'relu': 2, 'linear': 3, 'hard_sigmoid': 4}
+
+
+def _lstm_shape(what, zx, U):
+    if zx.dim() != 3 or U.dim() != 2 or U.shape[1] != 4 * U.shape[0] or zx.shape[2] != U.shape[1] or zx.dtype != torch.float32 or U.dtype != torch.float32:
+        raise ValueError('%s: float32 (B, T, 4u) beside a recurrent kernel (u, 4u) is expected, got %r and %r' % (what, tuple(zx.shape), tuple(U.shape)))
+    return int(zx.shape[0]), int(zx.shape[1]), int(U.shape[0])
+
+
+def lstm_fwd(zx, U, bias, h0=None, c0=None, activation='tanh', recurrent_activation='hard_sigmoid', reverse=False, training=False):
+    """The LSTM recurrence over zx (B, T, 4u) = X . W (gate columns i, f, c, o): -> (h, gates, c, hprev).  h (B, T, u) is in processing order
+    (under `reverse` step s reads zx[:, T-1-s]); in the training phase gates (B, T, 4u), c (B, T, u) and hprev (B, T, u), the h that entered each
+    step, are stored at the input time index for lstm_bwd, else they are None.  h0 / c0 (B, u): None is zeros."""
+    _chk(zx, U, bias, h0, c0)
+    B, T, u = _lstm_shape('lstm_fwd', zx, U)
+    assert bias.numel() == 4 * u and all(t is None or tuple(t.shape) == (B, u) for t in (h0, c0))
+    h = torch.empty((B, T, u), dtype=torch.float32, device=zx.device)
+    gates = c = hprev = None
+    if training:
+        gates = torch.empty((B, T, 4 * u), dtype=torch.float32, device=zx.device)
+        c, hprev = torch.empty_like(h), torch.empty_like(h)
+    ws = workspace(_lib.size('gn_lstm_fwd_workspace', u), zx.device)
+    _lib.call('gn_lstm_fwd', _p(zx), _p(U), _p(bias), _p(h0), _p(c0), _p(h), _p(gates), _p(c), _p(hprev), _p(ws), ws.numel(), B, T, u,
+              LSTM_ACT[activation], LSTM_ACT[recurrent_activation], int(bool(reverse)), int(bool(training)), _stream())
+    return h, gates, c, hprev
+
+
+def lstm_bwd(dy, gates, c, U, c0=None, activation='tanh', recurrent_activation='hard_sigmoid', reverse=False, want_state_grads=False):
+    """Backward through time from the stored gates and c: dy (B, T, u) in processing order, or (B, u) for the last step only.
+    -> (dz (B, T, 4u) at the input time index, dh0, dc0); the two state gradients (B, u) only under want_state_grads, else None."""
+    _chk(dy, gates, c, U, c0)
+    B, T, u = _lstm_shape('lstm_bwd', gates, U)
+    if tuple(dy.shape) not in ((B, T, u), (B, u)) or tuple(c.shape) != (B, T, u):
+        raise ValueError('lstm_bwd: dy %r and c %r beside gates %r' % (tuple(dy.shape), tuple(c.shape), tuple(gates.shape)))
+    dz = torch.empty_like(gates)
+    dh0 = dc0 = None
+    if want_state_grads:
+        dh0, dc0 = (torch.empty((B, u), dtype=torch.float32, device=dy.device) for _ in range(2))
+    ws = workspace(_lib.size('gn_lstm_bwd_workspace', u), dy.device)
+    _lib.call('gn_lstm_bwd', _p(dy), _p(gates), _p(c), _p(c0), _p(U), _p(dz), _p(dh0), _p(dc0), _p(ws), ws.numel(), B, T, u,
+              LSTM_ACT[activation], LSTM_ACT[recurrent_activation], int(bool(reverse)), int(dy.dim() == 3), _stream())
+    return dz, dh0, dc0
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

@@ -1,0 +1,152 @@
+"""keras.layers.LSTM (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrence of csrc/lstm.hip; DESIGN 8o.
+
+The class is part of the gennet_amd.layers name space (gennet_amd.layers.LSTM is this class), as every layer is."""
+import numpy as np
+
+from . import engine, ops, regularizers
+from .engine import Layer
+
+_ACTIVATIONS = ('tanh', 'sigmoid', 'relu', 'linear')
+_RECURRENT_ACTIVATIONS = ('hard_sigmoid', 'sigmoid')
+
+
+def _name_of(v):
+    return getattr(v, '__name__', v) if callable(v) else v
+
+
+def _initializer_is(v, name, class_names, **config):
+    """whether `v` (a name, None, or the config dict keras serializes) is the initializer `name`"""
+    if v is None or v == name:
+        return True
+    return isinstance(v, dict) and v.get('class_name') in class_names and all((v.get('config') or {}).get(k, d) == d for k, d in config.items())
+
+
+def orthogonal_blocks(u, n=4):
+    """(u, n u): n orthogonal u x u blocks side by side, each the Q of the QR factorisation of a standard normal draw with the signs fixed so
+    that R's diagonal is positive (the draw then is uniform over the orthogonal group); from the generator glorot_uniform draws from."""
+    blocks = []
+    for _ in range(n):
+        q, r = np.linalg.qr(engine._INIT_RNG.normal(0.0, 1.0, size=(u, u)))
+        blocks.append(q * np.where(np.diag(r) < 0, -1.0, 1.0)[None, :])
+    return np.concatenate(blocks, axis=1).astype(np.float32)
+
+
+_SPLIT_MIN_ROWS, _SPLIT_MAX, _SPLIT_MAX_BYTES = 256, 64, 64 << 20
+
+
+def row_splits(rows, cols):
+    """In how many equal parts the B T rows of a weight-gradient product are summed: gn_bmm has no split-K, so one (Cin, 4u) or (u, 4u) result
+    over all rows is a handful of blocks walking tens of thousands of rows each.  The largest divisor of `rows` that is at most 64, leaves at
+    least 256 rows a part and keeps the (parts, cols) partial results inside 64 MiB; 1 where there is none.  By shape alone."""
+    best = 1
+    for parts in range(2, _SPLIT_MAX + 1):
+        if rows % parts == 0 and rows // parts >= _SPLIT_MIN_ROWS and parts * cols * 4 <= _SPLIT_MAX_BYTES:
+            best = parts
+    return best
+
+
+def rows_product(a, dz, out):
+    """out (K, N) = a^T . dz for a (rows, K), dz (rows, N): one gn_bmm, or row_splits parts as one batched gn_bmm whose partial results are summed
+    by the fixed-order fp64 column reduction (ops.bias_grad over the (parts, K N) view).  Deterministic either way."""
+    rows, K, N = a.shape[0], a.shape[1], dz.shape[1]
+    parts = row_splits(rows, K * N)
+    if parts == 1:
+        return ops.bmm(a.view(1, rows, K), dz.view(1, rows, N), trans_a=True, out=out.view(1, K, N))
+    part = ops.bmm(a.view(parts, rows // parts, K), dz.view(parts, rows // parts, N), trans_a=True)
+    return ops.bias_grad(part.view(parts, K * N), out.view(K * N))
+
+
+class LSTM(Layer):
+    """keras.layers.LSTM(units): (B, T, Cin) -> (B, units), or (B, T, units) with return_sequences.  LSTMCell of keras 2.2.4, gate columns
+    i, f, c, o in kernel (Cin, 4u), recurrent_kernel (u, 4u) and bias (4u):
+        z_t = x_t . W + h_{t-1} . U + b;  i = ra(z_i), f = ra(z_f), g = act(z_c), o = ra(z_o);  c_t = f c_{t-1} + i g;  h_t = o act(c_t)
+    with act one of tanh, sigmoid, relu, linear and ra hard_sigmoid or sigmoid; h_0 = c_0 = 0.  go_backwards walks the sequence from its last
+    sample, and the returned sequence is in processing order, as keras leaves it.  implementation 1 and 2 are one arithmetic here and unroll is a
+    hint; both are kept for the config.
+    Forward: zx = X . W for all steps as one gn_bmm over B T rows, then gn_lstm_fwd, one launch that walks the T steps with h and c on chip.
+    Backward: gn_lstm_bwd walks the steps down and writes dz (B, T, 4u); dW = X^T dz, dU = hprev^T dz and dX = dz W^T are one gn_bmm each over
+    B T rows (the two weight gradients in up to 64 row parts summed in fixed order: rows_product) and db the bias-gradient reduction.  The tape
+    keeps x, hprev (h shifted by one step: h_{t-1} beside dz_t), the activated gates and c, in the training phase only.  The planner fuses
+    nothing onto the layer, and dy is not written."""
+
+    def __init__(self, units, activation='tanh', recurrent_activation='hard_sigmoid', use_bias=True, kernel_initializer='glorot_uniform',
+                 recurrent_initializer='orthogonal', bias_initializer='zeros', unit_forget_bias=True, kernel_regularizer=None,
+                 recurrent_regularizer=None, bias_regularizer=None, activity_regularizer=None, return_sequences=False, go_backwards=False,
+                 implementation=1, unroll=False, **kw):
+        for key in ('dropout', 'recurrent_dropout'):
+            if float(kw.pop(key, 0.0) or 0.0) != 0.0:
+                raise NotImplementedError('LSTM(%s=...): dropout inside the cell is not implemented; only 0 runs' % key)
+        for key in ('stateful', 'return_state'):
+            if kw.pop(key, False):
+                raise NotImplementedError('LSTM(%s=True) is not implemented' % key)
+        for key in ('kernel_constraint', 'recurrent_constraint', 'bias_constraint'):
+            if kw.pop(key, None) is not None:
+                raise NotImplementedError('LSTM(%s=...): weight constraints are not implemented' % key)
+        if not use_bias:
+            raise NotImplementedError('LSTM(use_bias=False)')
+        act, ract = _name_of(activation), _name_of(recurrent_activation)
+        act = 'linear' if act is None else act
+        if act not in _ACTIVATIONS:
+            raise NotImplementedError('LSTM(activation=%r): one of %s' % (activation, ', '.join(_ACTIVATIONS)))
+        if ract not in _RECURRENT_ACTIVATIONS:
+            raise NotImplementedError('LSTM(recurrent_activation=%r): one of %s' % (recurrent_activation, ', '.join(_RECURRENT_ACTIVATIONS)))
+        if not _initializer_is(kernel_initializer, 'glorot_uniform', ('GlorotUniform', 'VarianceScaling'), mode='fan_avg', distribution='uniform'):
+            raise NotImplementedError('LSTM(kernel_initializer=%r): only glorot_uniform' % (kernel_initializer,))
+        if not _initializer_is(recurrent_initializer, 'orthogonal', ('Orthogonal',), gain=1.0):
+            raise NotImplementedError('LSTM(recurrent_initializer=%r): only orthogonal' % (recurrent_initializer,))
+        if not _initializer_is(bias_initializer, 'zeros', ('Zeros',)):
+            raise NotImplementedError('LSTM(bias_initializer=%r): only zeros' % (bias_initializer,))
+        if implementation not in (1, 2):
+            raise ValueError('LSTM(implementation=%r): 1 or 2' % (implementation,))
+        Layer.__init__(self, **kw)
+        self.units = int(units)
+        if self.units < 1:
+            raise ValueError('LSTM(units=%r): at least 1' % (units,))
+        self.activation, self.recurrent_activation = act, ract
+        self.unit_forget_bias = bool(unit_forget_bias)
+        self.kernel_regularizer, self.recurrent_regularizer = regularizers.get(kernel_regularizer), regularizers.get(recurrent_regularizer)
+        self.bias_regularizer, self.activity_regularizer = regularizers.get(bias_regularizer), regularizers.get(activity_regularizer)
+        self.return_sequences, self.go_backwards = bool(return_sequences), bool(go_backwards)
+        self.implementation, self.unroll = int(implementation), bool(unroll)
+
+    def build(self, input_shape):
+        if len(input_shape) != 2:
+            raise ValueError('%s (LSTM) expects (batch, timesteps, features), got %r' % (self.name, (None,) + tuple(input_shape)))
+        Cin, u = int(input_shape[1]), self.units
+        if u > 512:
+            raise NotImplementedError('%s: LSTM(units=%d): at most 512 units run (a block carries all units of its samples on chip)' % (self.name, u))
+        self.kernel = self.add_weight('kernel', engine.glorot_uniform((Cin, 4 * u)), regularizer=self.kernel_regularizer)
+        self.recurrent_kernel = self.add_weight('recurrent_kernel', orthogonal_blocks(u), regularizer=self.recurrent_regularizer)
+        bias = np.zeros(4 * u, np.float32)
+        if self.unit_forget_bias:
+            bias[u:2 * u] = 1.0
+        self.bias = self.add_weight('bias', bias, regularizer=self.bias_regularizer)
+
+    def compute_output_shape(self, input_shape):
+        return (int(input_shape[0]), self.units) if self.return_sequences else (self.units,)
+
+    def forward(self, ctx, node, x):
+        x = x.contiguous()
+        B, T, Cin = x.shape
+        u = self.units
+        zx = ops.bmm(x.view(1, B * T, Cin), self.kernel.data.view(1, Cin, 4 * u)).view(B, T, 4 * u)
+        h, gates, c, hprev = ops.lstm_fwd(zx, self.recurrent_kernel.data, self.bias.data, None, None, self.activation, self.recurrent_activation,
+                                          reverse=self.go_backwards, training=ctx.training)
+        if ctx.training:
+            ctx.tape[node.index] = (x, hprev, gates, c)
+        return h if self.return_sequences else h[:, T - 1, :].contiguous()
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        x, hprev, gates, c = ctx.tape.pop(node.index)
+        B, T, Cin = x.shape
+        u = self.units
+        dz, _, _ = ops.lstm_bwd(dy.contiguous().view((B, T, u) if self.return_sequences else (B, u)), gates, c, self.recurrent_kernel.data, None,
+                                self.activation, self.recurrent_activation, reverse=self.go_backwards)
+        dz2 = dz.view(B * T, 4 * u)
+        if need_dw:
+            rows_product(x.view(B * T, Cin), dz2, self.kernel.grad)
+            rows_product(hprev.view(B * T, u), dz2, self.recurrent_kernel.grad)
+            ops.bias_grad(dz2, self.bias.grad)
+        if not need_dx:
+            return None
+        return ops.bmm(dz2.view(1, B * T, 4 * u), self.kernel.data.view(1, Cin, 4 * u), trans_b=True).view(B, T, Cin)

@@ -423,6 +423,29 @@ int gn_bmm_valu(const float* a, const float* b, float* c, int batch, int M, int 
 int gn_l2norm_fwd(const float* x, float* y, float* inv, size_t outer, int P, int inner, void* stream);
 int gn_l2norm_bwd(const float* dy, const float* y, const float* inv, float* dx, size_t outer, int P, int inner, void* stream);
 
+/* ---- LSTM recurrence (csrc/lstm.hip; keras layers.LSTM, LSTMCell of keras 2.2.4).  Gate columns i, f, c, o of width u:
+ *   z_t = zx_t + h_{t-1} . U + b;  i = ra(z_i), f = ra(z_f), g = act(z_c), o = ra(z_o);  c_t = f c_{t-1} + i g;  h_t = o act(c_t)
+ * with act one of GN_LSTM_TANH, _SIGMOID, _RELU, _LINEAR and ra one of GN_LSTM_HARD_SIGMOID (min(max(0.2 x + 0.5, 0), 1)), GN_LSTM_SIGMOID.
+ * One block carries 16 batch rows through all T steps: h and c stay on chip, the step product runs on v_mfma_f32_16x16x4_f32, no block waits
+ * on another, no atomics.  Every z is one fp32 fma chain over k from +0, then + zx, then + b, so a sample's results do not depend on B, on its
+ * tile or on the launch.  1 <= u <= 512; any B, T >= 1; 4-byte aligned pointers.
+ * gn_lstm_fwd: zx (B, T, 4u) = X . W, U (u, 4u), bias (4u), h0 / c0 (B, u) or NULL (zeros).  Step s = 0 .. T-1 reads zx at the input time
+ *   t = s, or T-1-s under `reverse`, and writes h[:, s] (processing order, as keras returns it).  With `training` it also stores, at the INPUT
+ *   time t of the step, the activated gates (B, T, 4u), c (B, T, u) and hprev (B, T, u), the h that entered the step (h0 at the first).
+ * gn_lstm_bwd: dy (B, T, u) in processing order (dy_seq) or (B, u) for the last step only; gates, c as stored, c0 as given to the forward.
+ *   Walks the steps backwards, forms dh_{t-1} = dz_t . U^T on the matrix cores and writes dz (B, T, 4u) at the input time index, so
+ *   dW = X^T dz, dU = hprev^T dz, dX = dz W^T and db are products over B T rows; dh0 / dc0 (B, u) when not NULL.
+ * ws: gn_lstm_fwd_workspace(u) / gn_lstm_bwd_workspace(u) bytes (the zero-padded U / U^T the kernels read); 0 for a u out of range.
+ * GN_EINVAL, nothing launched: a NULL pointer, T < 1, u < 1 or u > 512, an unknown activation code; GN_EWORKSPACE: ws too small.
+ * B == 0 is GN_OK without a launch. */
+enum gn_lstm_act { GN_LSTM_TANH = 0, GN_LSTM_SIGMOID = 1, GN_LSTM_RELU = 2, GN_LSTM_LINEAR = 3, GN_LSTM_HARD_SIGMOID = 4 };
+size_t gn_lstm_fwd_workspace(int u);
+size_t gn_lstm_bwd_workspace(int u);
+int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float* h0, const float* c0, float* h, float* gates, float* c, float* hprev,
+                void* ws, size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int training, void* stream);
+int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float* c0, const float* U, float* dz, float* dh0, float* dc0, void* ws,
+                size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int dy_seq, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
