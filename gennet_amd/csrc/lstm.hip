@@ -37,34 +37,10 @@
 
 #include "common.h"
 #include "lstm_geom.h"
+#include "recurrent.h"          // the activations and the launches that pad U, shared with csrc/gru.hip
 
 namespace gn {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lstm_sigmoid(float x) { return act_apply(x, GN_ACT_SIGMOID, 0.f); }
-
-__device__ __forceinline__ float lstm_act(float x, int code) {
-  switch (code) {
-    case GN_LSTM_TANH: return gn_tanhf(x);
-    case GN_LSTM_SIGMOID: return lstm_sigmoid(x);
-    case GN_LSTM_RELU: return fmaxf(x, 0.f);
-    case GN_LSTM_HARD_SIGMOID: return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f);
-    default: return x;
-  }
-}
-
-// the derivative through the OUTPUT value y = act(x)
-__device__ __forceinline__ float lstm_act_grad(float y, int code) {
-  switch (code) {
-    case GN_LSTM_TANH: return 1.f - y * y;
-    case GN_LSTM_SIGMOID: return y * (1.f - y);
-    case GN_LSTM_RELU: return y > 0.f ? 1.f : 0.f;
-    case GN_LSTM_HARD_SIGMOID: return (y > 0.f && y < 1.f) ? 0.2f : 0.f;
-    default: return 1.f;
-  }
-}
 
 struct LstmFwdArgs {
   const float* zx;      // (B, T, 4u)
@@ -302,24 +278,6 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
   }
 }
 
-// up[k * SU + q * UP + j] = U[k][q u + j], +0 outside u
-__global__ __launch_bounds__(256) void lstm_pad_u_kernel(const float* __restrict__ U, float* __restrict__ up, int u, int KP, int UP, int SU) {
-  const int n = KP * SU;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-    const int k = e / SU, col = e % SU, q = col / UP, j = col % UP;
-    up[e] = (k < u && q < 4 && j < u) ? U[(size_t)k * 4 * u + q * u + j] : 0.f;
-  }
-}
-
-// utp[(q * KP + k) * SUT + j] = U[j][q u + k], +0 outside u
-__global__ __launch_bounds__(256) void lstm_pad_ut_kernel(const float* __restrict__ U, float* __restrict__ utp, int u, int KP, int SUT) {
-  const int n = 4 * KP * SUT;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-    const int row = e / SUT, j = e % SUT, q = row / KP, k = row % KP;
-    utp[e] = (k < u && j < u) ? U[(size_t)j * 4 * u + q * u + k] : 0.f;
-  }
-}
-
 template <int NT, bool ULDS>
 void launch_fwd(const LstmFwdArgs& a, const LstmGeom& m, hipStream_t s) {
   static unsigned long long big = 0;
@@ -332,11 +290,6 @@ void launch_bwd(const LstmBwdArgs& a, const LstmGeom& m, hipStream_t s) {
   static unsigned long long big = 0;
   allow_big_lds((const void*)lstm_bwd_kernel<NT, ULDS>, &big);
   hipLaunchKernelGGL((lstm_bwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
-}
-
-bool lstm_code_ok(int code, bool recurrent) {
-  return recurrent ? (code == GN_LSTM_HARD_SIGMOID || code == GN_LSTM_SIGMOID)
-                   : (code == GN_LSTM_TANH || code == GN_LSTM_SIGMOID || code == GN_LSTM_RELU || code == GN_LSTM_LINEAR);
 }
 
 // 0: launch, 1: nothing to do, GN_EINVAL: refused
@@ -373,7 +326,7 @@ int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float*
   }
   hipStream_t s = (hipStream_t)stream;
   float* up = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U, up, u, m.KP, m.UP, m.SU);
+  hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U, up, u, m.KP, m.UP, m.SU, 4);
   const LstmFwdArgs a = {zx, up, bias, h0, c0, h, gates, c, hprev, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0};
   if (m.fwd_u_lds) launch_fwd<1, true>(a, m, s);           // u <= 88: six tiles at the most, one a wave
   else if (m.NT == 1) launch_fwd<1, false>(a, m, s);
@@ -395,7 +348,7 @@ int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float
   }
   hipStream_t s = (hipStream_t)stream;
   float* utp = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U, utp, u, m.KP, m.SUT);
+  hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U, utp, u, m.KP, m.SUT, 4);
   const LstmBwdArgs a = {dy, gates, c, c0, utp, dz, dh0, dc0, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0};
   if (m.bwd_u_lds) launch_bwd<1, true>(a, m, s);           // u <= 80: five tiles at the most, one a wave
   else if (m.NT == 1) launch_bwd<1, false>(a, m, s);

@@ -231,13 +231,17 @@ def layer_config(layer):
         cfg.update(axis=layer.axis)
     elif isinstance(layer, L.Dot):               # axes as keras writes it: the int, or the pair as a list
         cfg.update(axes=layer.axes if isinstance(layer.axes, int) else list(layer.axes), normalize=layer.normalize)
-    elif isinstance(layer, L.LSTM):              # the keys of keras 2.2.4 layers/recurrent.py LSTM.get_config
+    elif isinstance(layer, (L.LSTM, L.GRU)):     # the keys of keras 2.2.4 layers/recurrent.py LSTM.get_config / GRU.get_config
         cfg.update(return_sequences=layer.return_sequences, return_state=False, go_backwards=layer.go_backwards, stateful=False, unroll=layer.unroll,
                    units=layer.units, activation=layer.activation, recurrent_activation=layer.recurrent_activation, use_bias=True,
-                   kernel_initializer=_GLOROT, recurrent_initializer=_ORTHOGONAL, bias_initializer=_ZEROS, unit_forget_bias=layer.unit_forget_bias,
+                   kernel_initializer=_GLOROT, recurrent_initializer=_ORTHOGONAL, bias_initializer=_ZEROS,
                    kernel_regularizer=_reg(layer.kernel_regularizer), recurrent_regularizer=_reg(layer.recurrent_regularizer),
                    bias_regularizer=_reg(layer.bias_regularizer), activity_regularizer=_reg(layer.activity_regularizer), kernel_constraint=None,
                    recurrent_constraint=None, bias_constraint=None, dropout=0.0, recurrent_dropout=0.0, implementation=layer.implementation)
+        if isinstance(layer, L.LSTM):
+            cfg.update(unit_forget_bias=layer.unit_forget_bias)
+        else:
+            cfg.update(reset_after=layer.reset_after)
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -358,12 +362,13 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.Concatenate(axis=cfg.get('axis', -1), **kw)
     if class_name == 'Dot':
         return L.Dot(axes=cfg['axes'], normalize=cfg.get('normalize', False), **kw)
-    if class_name == 'LSTM':                     # the layer itself refuses what it does not run, naming the key
-        keys = ('activation', 'recurrent_activation', 'use_bias', 'kernel_initializer', 'recurrent_initializer', 'bias_initializer', 'unit_forget_bias',
+    if class_name in ('LSTM', 'GRU'):            # the layer itself refuses what it does not run, naming the key
+        keys = ('activation', 'recurrent_activation', 'use_bias', 'kernel_initializer', 'recurrent_initializer', 'bias_initializer',
+                'unit_forget_bias' if class_name == 'LSTM' else 'reset_after',
                 'kernel_regularizer', 'recurrent_regularizer', 'bias_regularizer', 'activity_regularizer', 'kernel_constraint', 'recurrent_constraint',
                 'bias_constraint', 'dropout', 'recurrent_dropout', 'implementation', 'return_sequences', 'return_state', 'go_backwards', 'stateful',
                 'unroll')
-        return L.LSTM(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
+        return getattr(L, class_name)(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 

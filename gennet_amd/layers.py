@@ -1505,5 +1505,5 @@ def concatenate(inputs, axis=-1, **kw):
 # keras.layers.Dot / dot live in gennet_amd/dot.py and are part of this name space
 from .dot import Dot, dot  # noqa: E402,F401
 
-# keras.layers.LSTM lives in gennet_amd/recurrent.py and is part of this name space
-from .recurrent import LSTM  # noqa: E402,F401
+# keras.layers.LSTM and keras.layers.GRU live in gennet_amd/recurrent.py and are part of this name space
+from .recurrent import GRU, LSTM  # noqa: E402,F401

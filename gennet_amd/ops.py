@@ -583,6 +583,52 @@ def lstm_bwd(dy, gates, c, U, c0=None, activation='tanh', recurrent_activation='
     return dz, dh0, dc0
 
 
+# ---------------------------------------------------------------------------------------------- GRU recurrence (csrc/gru.hip)
+def _gru_shape(what, zx, U):
+    if zx.dim() != 3 or U.dim() != 2 or U.shape[1] != 3 * U.shape[0] or zx.shape[2] != U.shape[1] or zx.dtype != torch.float32 or U.dtype != torch.float32:
+        raise ValueError('%s: float32 (B, T, 3u) beside a recurrent kernel (u, 3u) is expected, got %r and %r' % (what, tuple(zx.shape), tuple(U.shape)))
+    return int(zx.shape[0]), int(zx.shape[1]), int(U.shape[0])
+
+
+def gru_fwd(zx, U, bias, rbias=None, h0=None, activation='tanh', recurrent_activation='hard_sigmoid', reset_after=False, reverse=False,
+            training=False):
+    """The GRU recurrence over zx (B, T, 3u) = X . W (gate columns z, r, h): -> (h, gates, hprev, aux).  h (B, T, u) is in processing order
+    (under `reverse` step s reads zx[:, T-1-s]); in the training phase gates (B, T, 3u) = z, r, hh, hprev (B, T, u), the h that entered each
+    step, and aux (B, T, u) = r h_{t-1} (q under reset_after) are stored at the input time index for gru_bwd, else they are None.
+    bias (3u); rbias (3u), the recurrent bias, exactly under reset_after; h0 (B, u): None is zeros."""
+    _chk(zx, U, bias, rbias, h0)
+    B, T, u = _gru_shape('gru_fwd', zx, U)
+    if (rbias is not None) != bool(reset_after):
+        raise ValueError('gru_fwd: the recurrent bias goes with reset_after, and only with it')
+    assert bias.numel() == 3 * u and (rbias is None or rbias.numel() == 3 * u) and (h0 is None or tuple(h0.shape) == (B, u))
+    h = torch.empty((B, T, u), dtype=torch.float32, device=zx.device)
+    gates = hprev = aux = None
+    if training:
+        gates = torch.empty((B, T, 3 * u), dtype=torch.float32, device=zx.device)
+        hprev, aux = torch.empty_like(h), torch.empty_like(h)
+    ws = workspace(_lib.size('gn_gru_fwd_workspace', u), zx.device)
+    _lib.call('gn_gru_fwd', _p(zx), _p(U), _p(bias), _p(rbias), _p(h0), _p(h), _p(gates), _p(hprev), _p(aux), _p(ws), ws.numel(), B, T, u,
+              LSTM_ACT[activation], LSTM_ACT[recurrent_activation], int(bool(reset_after)), int(bool(reverse)), int(bool(training)), _stream())
+    return h, gates, hprev, aux
+
+
+def gru_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activation='hard_sigmoid', reset_after=False, reverse=False, want_state_grad=False):
+    """Backward through time from what gru_fwd stored: dy (B, T, u) in processing order, or (B, u) for the last step only.
+    -> (dz, dzr, dh0): dz (B, T, 3u) = da_z, da_r, da_h at the input time index; dzr (B, T, 3u) = da_z, da_r, dq under reset_after, else None;
+    dh0 (B, u) only under want_state_grad, else None."""
+    _chk(dy, gates, hprev, aux, U)
+    B, T, u = _gru_shape('gru_bwd', gates, U)
+    if tuple(dy.shape) not in ((B, T, u), (B, u)) or tuple(hprev.shape) != (B, T, u) or tuple(aux.shape) != (B, T, u):
+        raise ValueError('gru_bwd: dy %r, hprev %r and aux %r beside gates %r' % (tuple(dy.shape), tuple(hprev.shape), tuple(aux.shape), tuple(gates.shape)))
+    dz = torch.empty_like(gates)
+    dzr = torch.empty_like(gates) if reset_after else None
+    dh0 = torch.empty((B, u), dtype=torch.float32, device=dy.device) if want_state_grad else None
+    ws = workspace(_lib.size('gn_gru_bwd_workspace', u), dy.device)
+    _lib.call('gn_gru_bwd', _p(dy), _p(gates), _p(hprev), _p(aux), _p(U), _p(dz), _p(dzr), _p(dh0), _p(ws), ws.numel(), B, T, u,
+              LSTM_ACT[activation], LSTM_ACT[recurrent_activation], int(bool(reset_after)), int(bool(reverse)), int(dy.dim() == 3), _stream())
+    return dz, dzr, dh0
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

@@ -1,6 +1,7 @@
-"""keras.layers.LSTM (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrence of csrc/lstm.hip; DESIGN 8o.
+"""keras.layers.LSTM and keras.layers.GRU (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrences of csrc/lstm.hip and
+csrc/gru.hip; DESIGN 8o, 8p.
 
-The class is part of the gennet_amd.layers name space (gennet_amd.layers.LSTM is this class), as every layer is."""
+The classes are part of the gennet_amd.layers name space (gennet_amd.layers.LSTM is this LSTM), as every layer is."""
 import numpy as np
 
 from . import engine, ops, regularizers
@@ -56,6 +57,122 @@ def rows_product(a, dz, out):
     return ops.bias_grad(part.view(parts, K * N), out.view(K * N))
 
 
+def _init_recurrent(layer, what, kw, units, activation, recurrent_activation, use_bias, kernel_initializer, recurrent_initializer, bias_initializer,
+                    kernel_regularizer, recurrent_regularizer, bias_regularizer, activity_regularizer, return_sequences, go_backwards,
+                    implementation, unroll):
+    """What LSTM and GRU share of their constructors: the refusals, each naming its key (`what` is the class name), Layer.__init__ over the rest
+    of kw, and the attributes both configs write."""
+    for key in ('dropout', 'recurrent_dropout'):
+        if float(kw.pop(key, 0.0) or 0.0) != 0.0:
+            raise NotImplementedError('%s(%s=...): dropout inside the cell is not implemented; only 0 runs' % (what, key))
+    for key in ('stateful', 'return_state'):
+        if kw.pop(key, False):
+            raise NotImplementedError('%s(%s=True) is not implemented' % (what, key))
+    for key in ('kernel_constraint', 'recurrent_constraint', 'bias_constraint'):
+        if kw.pop(key, None) is not None:
+            raise NotImplementedError('%s(%s=...): weight constraints are not implemented' % (what, key))
+    if not use_bias:
+        raise NotImplementedError('%s(use_bias=False)' % what)
+    act, ract = _name_of(activation), _name_of(recurrent_activation)
+    act = 'linear' if act is None else act
+    if act not in _ACTIVATIONS:
+        raise NotImplementedError('%s(activation=%r): one of %s' % (what, activation, ', '.join(_ACTIVATIONS)))
+    if ract not in _RECURRENT_ACTIVATIONS:
+        raise NotImplementedError('%s(recurrent_activation=%r): one of %s' % (what, recurrent_activation, ', '.join(_RECURRENT_ACTIVATIONS)))
+    if not _initializer_is(kernel_initializer, 'glorot_uniform', ('GlorotUniform', 'VarianceScaling'), mode='fan_avg', distribution='uniform'):
+        raise NotImplementedError('%s(kernel_initializer=%r): only glorot_uniform' % (what, kernel_initializer))
+    if not _initializer_is(recurrent_initializer, 'orthogonal', ('Orthogonal',), gain=1.0):
+        raise NotImplementedError('%s(recurrent_initializer=%r): only orthogonal' % (what, recurrent_initializer))
+    if not _initializer_is(bias_initializer, 'zeros', ('Zeros',)):
+        raise NotImplementedError('%s(bias_initializer=%r): only zeros' % (what, bias_initializer))
+    if implementation not in (1, 2):
+        raise ValueError('%s(implementation=%r): 1 or 2' % (what, implementation))
+    Layer.__init__(layer, **kw)
+    layer.units = int(units)
+    if layer.units < 1:
+        raise ValueError('%s(units=%r): at least 1' % (what, units))
+    layer.activation, layer.recurrent_activation = act, ract
+    layer.kernel_regularizer, layer.recurrent_regularizer = regularizers.get(kernel_regularizer), regularizers.get(recurrent_regularizer)
+    layer.bias_regularizer, layer.activity_regularizer = regularizers.get(bias_regularizer), regularizers.get(activity_regularizer)
+    layer.return_sequences, layer.go_backwards = bool(return_sequences), bool(go_backwards)
+    layer.implementation, layer.unroll = int(implementation), bool(unroll)
+
+
+class GRU(Layer):
+    """keras.layers.GRU(units): (B, T, Cin) -> (B, units), or (B, T, units) with return_sequences.  GRUCell of keras 2.2.4, gate columns z, r, h
+    in kernel (Cin, 3u), recurrent_kernel (u, 3u) and bias (3u), or (2, 3u) under reset_after (row 0 the input bias b, row 1 the recurrent rb):
+        a_t = x_t . W + b
+        reset_after=False:  m = h_{t-1} . U[:, :2u];  z = ra(a_z + m_z), r = ra(a_r + m_r);  hh = act(a_h + (r h_{t-1}) . U_h)
+        reset_after=True:   m = h_{t-1} . U + rb;     z = ra(a_z + m_z), r = ra(a_r + m_r);  hh = act(a_h + r m_h)
+        h_t = z h_{t-1} + (1 - z) hh
+    with act one of tanh, sigmoid, relu, linear and ra hard_sigmoid or sigmoid; h_0 = 0.  go_backwards, implementation and unroll as in LSTM.
+    Forward: zx = X . W as one gn_bmm over B T rows, then gn_gru_fwd, one launch that walks the T steps with h on chip.
+    Backward: gn_gru_bwd walks the steps down and writes dz (B, T, 3u) = da_z, da_r, da_h: dW = X^T dz, dX = dz W^T, db = sum dz.
+    reset_after=True: it also writes dzr = da_z, da_r, dq: dU = hprev^T dzr, d rb = sum dzr.  reset_after=False: dU has two column blocks from two
+    left operands, dU[:, :2u] = hprev^T dz[:, :2u] and dU[:, 2u:] = (r hprev)^T da_h; dz is cut into its two column blocks (the concatenate
+    pass backwards), each block is one rows_product, and the concatenate pass joins them: fixed order, no atomics.  The tape keeps x, hprev, the
+    gates and aux (r hprev, or m_h), in the training phase only.  The planner fuses nothing onto the layer, and dy is not written."""
+
+    def __init__(self, units, activation='tanh', recurrent_activation='hard_sigmoid', use_bias=True, kernel_initializer='glorot_uniform',
+                 recurrent_initializer='orthogonal', bias_initializer='zeros', kernel_regularizer=None, recurrent_regularizer=None,
+                 bias_regularizer=None, activity_regularizer=None, return_sequences=False, go_backwards=False, implementation=1, unroll=False,
+                 reset_after=False, **kw):
+        _init_recurrent(self, 'GRU', kw, units, activation, recurrent_activation, use_bias, kernel_initializer, recurrent_initializer, bias_initializer,
+                        kernel_regularizer, recurrent_regularizer, bias_regularizer, activity_regularizer, return_sequences, go_backwards,
+                        implementation, unroll)
+        self.reset_after = bool(reset_after)
+
+    def build(self, input_shape):
+        if len(input_shape) != 2:
+            raise ValueError('%s (GRU) expects (batch, timesteps, features), got %r' % (self.name, (None,) + tuple(input_shape)))
+        Cin, u = int(input_shape[1]), self.units
+        if u > 512:
+            raise NotImplementedError('%s: GRU(units=%d): at most 512 units run (a block carries all units of its samples on chip)' % (self.name, u))
+        self.kernel = self.add_weight('kernel', engine.glorot_uniform((Cin, 3 * u)), regularizer=self.kernel_regularizer)
+        self.recurrent_kernel = self.add_weight('recurrent_kernel', orthogonal_blocks(u, 3), regularizer=self.recurrent_regularizer)
+        self.bias = self.add_weight('bias', np.zeros((2, 3 * u) if self.reset_after else (3 * u,), np.float32), regularizer=self.bias_regularizer)
+
+    def compute_output_shape(self, input_shape):
+        return (int(input_shape[0]), self.units) if self.return_sequences else (self.units,)
+
+    def forward(self, ctx, node, x):
+        x = x.contiguous()
+        B, T, Cin = x.shape
+        u = self.units
+        zx = ops.bmm(x.view(1, B * T, Cin), self.kernel.data.view(1, Cin, 3 * u)).view(B, T, 3 * u)
+        b2 = self.bias.data.view(-1, 3 * u)
+        h, gates, hprev, aux = ops.gru_fwd(zx, self.recurrent_kernel.data, b2[0], b2[1] if self.reset_after else None, None, self.activation,
+                                           self.recurrent_activation, reset_after=self.reset_after, reverse=self.go_backwards, training=ctx.training)
+        if ctx.training:
+            ctx.tape[node.index] = (x, hprev, gates, aux)
+        return h if self.return_sequences else h[:, T - 1, :].contiguous()
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        x, hprev, gates, aux = ctx.tape.pop(node.index)
+        B, T, Cin = x.shape
+        u = self.units
+        dz, dzr, _ = ops.gru_bwd(dy.contiguous().view((B, T, u) if self.return_sequences else (B, u)), gates, hprev, aux, self.recurrent_kernel.data,
+                                 self.activation, self.recurrent_activation, reset_after=self.reset_after, reverse=self.go_backwards)
+        dz2 = dz.view(B * T, 3 * u)
+        if need_dw:
+            rows_product(x.view(B * T, Cin), dz2, self.kernel.grad)
+            db = self.bias.grad.view(-1, 3 * u)
+            ops.bias_grad(dz2, db[0])
+            if self.reset_after:
+                dzr2 = dzr.view(B * T, 3 * u)
+                rows_product(hprev.view(B * T, u), dzr2, self.recurrent_kernel.grad)
+                ops.bias_grad(dzr2, db[1])
+            else:
+                dzr_zr, dz_h = ops.concat_bwd(dz2, [(B * T, 2 * u), (B * T, u)], 1)
+                dU_zr, dU_h = dz.new_empty((u, 2 * u)), dz.new_empty((u, u))
+                rows_product(hprev.view(B * T, u), dzr_zr, dU_zr)
+                rows_product(aux.view(B * T, u), dz_h, dU_h)
+                ops.concat_fwd([dU_zr, dU_h], 1, out=self.recurrent_kernel.grad)
+        if not need_dx:
+            return None
+        return ops.bmm(dz2.view(1, B * T, 3 * u), self.kernel.data.view(1, Cin, 3 * u), trans_b=True).view(B, T, Cin)
+
+
 class LSTM(Layer):
     """keras.layers.LSTM(units): (B, T, Cin) -> (B, units), or (B, T, units) with return_sequences.  LSTMCell of keras 2.2.4, gate columns
     i, f, c, o in kernel (Cin, 4u), recurrent_kernel (u, 4u) and bias (4u):
@@ -73,41 +190,10 @@ class LSTM(Layer):
                  recurrent_initializer='orthogonal', bias_initializer='zeros', unit_forget_bias=True, kernel_regularizer=None,
                  recurrent_regularizer=None, bias_regularizer=None, activity_regularizer=None, return_sequences=False, go_backwards=False,
                  implementation=1, unroll=False, **kw):
-        for key in ('dropout', 'recurrent_dropout'):
-            if float(kw.pop(key, 0.0) or 0.0) != 0.0:
-                raise NotImplementedError('LSTM(%s=...): dropout inside the cell is not implemented; only 0 runs' % key)
-        for key in ('stateful', 'return_state'):
-            if kw.pop(key, False):
-                raise NotImplementedError('LSTM(%s=True) is not implemented' % key)
-        for key in ('kernel_constraint', 'recurrent_constraint', 'bias_constraint'):
-            if kw.pop(key, None) is not None:
-                raise NotImplementedError('LSTM(%s=...): weight constraints are not implemented' % key)
-        if not use_bias:
-            raise NotImplementedError('LSTM(use_bias=False)')
-        act, ract = _name_of(activation), _name_of(recurrent_activation)
-        act = 'linear' if act is None else act
-        if act not in _ACTIVATIONS:
-            raise NotImplementedError('LSTM(activation=%r): one of %s' % (activation, ', '.join(_ACTIVATIONS)))
-        if ract not in _RECURRENT_ACTIVATIONS:
-            raise NotImplementedError('LSTM(recurrent_activation=%r): one of %s' % (recurrent_activation, ', '.join(_RECURRENT_ACTIVATIONS)))
-        if not _initializer_is(kernel_initializer, 'glorot_uniform', ('GlorotUniform', 'VarianceScaling'), mode='fan_avg', distribution='uniform'):
-            raise NotImplementedError('LSTM(kernel_initializer=%r): only glorot_uniform' % (kernel_initializer,))
-        if not _initializer_is(recurrent_initializer, 'orthogonal', ('Orthogonal',), gain=1.0):
-            raise NotImplementedError('LSTM(recurrent_initializer=%r): only orthogonal' % (recurrent_initializer,))
-        if not _initializer_is(bias_initializer, 'zeros', ('Zeros',)):
-            raise NotImplementedError('LSTM(bias_initializer=%r): only zeros' % (bias_initializer,))
-        if implementation not in (1, 2):
-            raise ValueError('LSTM(implementation=%r): 1 or 2' % (implementation,))
-        Layer.__init__(self, **kw)
-        self.units = int(units)
-        if self.units < 1:
-            raise ValueError('LSTM(units=%r): at least 1' % (units,))
-        self.activation, self.recurrent_activation = act, ract
+        _init_recurrent(self, 'LSTM', kw, units, activation, recurrent_activation, use_bias, kernel_initializer, recurrent_initializer, bias_initializer,
+                        kernel_regularizer, recurrent_regularizer, bias_regularizer, activity_regularizer, return_sequences, go_backwards,
+                        implementation, unroll)
         self.unit_forget_bias = bool(unit_forget_bias)
-        self.kernel_regularizer, self.recurrent_regularizer = regularizers.get(kernel_regularizer), regularizers.get(recurrent_regularizer)
-        self.bias_regularizer, self.activity_regularizer = regularizers.get(bias_regularizer), regularizers.get(activity_regularizer)
-        self.return_sequences, self.go_backwards = bool(return_sequences), bool(go_backwards)
-        self.implementation, self.unroll = int(implementation), bool(unroll)
 
     def build(self, input_shape):
         if len(input_shape) != 2:

@@ -446,6 +446,32 @@ int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float*
 int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float* c0, const float* U, float* dz, float* dh0, float* dc0, void* ws,
                 size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int dy_seq, void* stream);
 
+/* ---- GRU recurrence (csrc/gru.hip; keras layers.GRU, GRUCell of keras 2.2.4, both reset_after forms).  Gate columns z, r, h of width u:
+ *   a_t = zx_t + b;  reset_after 0: m = h_{t-1} . U[:, :2u], z = ra(a_z + m_z), r = ra(a_r + m_r), hh = act(a_h + (r h_{t-1}) . U_h)
+ *                    reset_after 1: m = h_{t-1} . U + rb,    z = ra(a_z + m_z), r = ra(a_r + m_r), q = m_h, hh = act(a_h + r q)
+ *   h_t = z h_{t-1} + (1 - z) hh
+ * with enum gn_lstm_act's activation codes: act TANH, SIGMOID, RELU or LINEAR, ra HARD_SIGMOID or SIGMOID.  Ownership and numerics are the
+ * LSTM recurrence's: one block carries 16 batch rows through all T steps, h stays on chip, the products run on v_mfma_f32_16x16x4_f32, no block
+ * waits on another, no atomics.  Every recurrent pre-activation is one fp32 fma chain over k from +0, then + rb where there is one, then
+ * + (zx + b), so a sample's results do not depend on B, on its tile or on the launch.  1 <= u <= 512; any B, T >= 1; 4-byte aligned pointers.
+ * gn_gru_fwd: zx (B, T, 3u) = X . W, U (u, 3u), bias (3u), rbias (3u; required exactly under reset_after, not looked at otherwise), h0 (B, u) or
+ *   NULL (zeros).  Step s reads zx at the input time t = s, or T-1-s under `reverse`, and writes h[:, s] (processing order).  With `training` it
+ *   also stores at the INPUT time t: gates (B, T, 3u) = z, r, hh; hprev (B, T, u), the h that entered the step; aux (B, T, u) = r h_{t-1}
+ *   (reset_after 0) or q (reset_after 1).
+ * gn_gru_bwd: dy (B, T, u) in processing order (dy_seq) or (B, u) for the last step only; gates, hprev, aux as stored.  Walks the steps backwards
+ *   and writes at the input time index dz (B, T, 3u) = da_z, da_r, da_h (dW = X^T dz, dX = dz W^T, db = sum dz) and, under reset_after, dzr
+ *   (B, T, 3u) = da_z, da_r, dq (dU = hprev^T dzr, d rb = sum dzr; required exactly then).  reset_after 0: dU[:, :2u] = hprev^T dz[:, :2u],
+ *   dU[:, 2u:] = aux^T dz[:, 2u:].  dh0 (B, u) when not NULL.
+ * ws: gn_gru_fwd_workspace(u) / gn_gru_bwd_workspace(u) bytes (the zero-padded U / U^T the kernels read); 0 for a u out of range.
+ * GN_EINVAL, nothing launched: a NULL pointer, T < 1, u < 1 or u > 512, B < 0, an unknown activation code, reset_after not 0 or 1;
+ * GN_EWORKSPACE: ws too small.  B == 0 is GN_OK without a launch. */
+size_t gn_gru_fwd_workspace(int u);
+size_t gn_gru_bwd_workspace(int u);
+int gn_gru_fwd(const float* zx, const float* U, const float* bias, const float* rbias, const float* h0, float* h, float* gates, float* hprev, float* aux,
+               void* ws, size_t ws_bytes, int B, int T, int u, int act, int ract, int reset_after, int reverse, int training, void* stream);
+int gn_gru_bwd(const float* dy, const float* gates, const float* hprev, const float* aux, const float* U, float* dz, float* dzr, float* dh0, void* ws,
+               size_t ws_bytes, int B, int T, int u, int act, int ract, int reset_after, int reverse, int dy_seq, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
