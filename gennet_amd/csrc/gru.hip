@@ -32,6 +32,10 @@
 //
 // STORED for the backward (training flag), at the INPUT time index of the step: gates (B, T, 3u) = z, r, hh; hprev (B, T, u), the h that entered
 // the step; aux (B, T, u) = r h_{t-1} (reset_after = 0: the left operand of dU's h block) or q (reset_after = 1).
+//
+// A PAIR OF DIRECTIONS (keras Bidirectional): as in csrc/lstm.hip.  blockIdx.y is the direction d and picks its operands from the
+// two-entry table of the arguments; direction 1 walks the other way and writes step s at position T-1-s; h and dy go through a row stride ld.
+// gn_gru_fwd / gn_gru_bwd launch one direction with ld = u; gn_gru_pair_fwd / _bwd launch two.
 #include <math.h>
 
 #include "common.h"
@@ -41,17 +45,22 @@
 namespace gn {
 namespace {
 
-struct GruFwdArgs {
+struct GruFwdDir {
   const float* zx;      // (B, T, 3u)
   const float* up;      // padded U: KP rows of SU floats
   const float* bias;    // (3u)
   const float* rbias;   // (3u), reset_after only
   const float* h0;      // (B, u) or NULL
-  float* h;             // (B, T, u), processing order
+  float* h;             // seq: (B, T, ld) rows of which the direction owns u columns; else (B, ld), the last processed step
   float* gates;         // (B, T, 3u), input time order; training only
   float* hprev;         // (B, T, u)
   float* aux;           // (B, T, u)
-  int B, T, u, KP, UP, SU, ntiles, act, ract, reverse, training;
+};
+
+// blockIdx.y is the direction: 0 walks with `reverse` and writes step s at position s, 1 walks with !reverse and writes it at position T-1-s
+struct GruFwdArgs {
+  GruFwdDir d[2];
+  int B, T, u, KP, UP, SU, ntiles, act, ract, reverse, training, ld, seq;
 };
 
 // acc[q] += A (16 rows of LDS, k in [0, KP)) . B (gate block q of NQ consecutive ones, 16 columns): two k groups of 4 a turn, loads first
@@ -75,6 +84,10 @@ __device__ __forceinline__ void gru_fwd_chain(f32x4 (&acc)[NQ], const float* ap,
 
 template <int NT, bool ULDS, bool RA>
 __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs g) {
+  const bool second = blockIdx.y != 0;
+  const GruFwdDir p = second ? g.d[1] : g.d[0];
+  const bool reverse = second ? !g.reverse : (g.reverse != 0);
+  const size_t h_row = g.seq ? (size_t)g.T * g.ld : (size_t)g.ld;              // floats between two samples of h
   extern __shared__ __attribute__((aligned(16))) float gru_lds[];
   const int SH = g.KP + 1;
   float* hs0 = gru_lds;
@@ -87,40 +100,42 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
 
   for (int e = threadIdx.x; e < LSTM_ROWS * SH; e += blockDim.x) {
     const int row = e / SH, k = e % SH;
-    hs0[e] = (g.h0 && k < g.u && b0 + row < (size_t)g.B) ? g.h0[(b0 + row) * u + k] : 0.f;
+    hs0[e] = (p.h0 && k < g.u && b0 + row < (size_t)g.B) ? p.h0[(b0 + row) * u + k] : 0.f;
     hs1[e] = 0.f;
   }
   if (ULDS)
-    for (int e = threadIdx.x; e < g.KP * g.SU; e += blockDim.x) us[e] = g.up[e];
-  const float* __restrict__ ub = ULDS ? (const float*)us : g.up;
+    for (int e = threadIdx.x; e < g.KP * g.SU; e += blockDim.x) us[e] = p.up[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : p.up;
 
   size_t ro[4];                                   // (row T) u of the lane's four rows: an element of step t is ro + t u + j
 #pragma unroll
   for (int r = 0; r < 4; ++r) ro[r] = (b0 + 4 * fq + r) * T * u;
   float hreg[NT][4], bias[NT][3], rb[NT][3];
-  const size_t t_first = g.reverse ? T - 1 : 0;
+  const size_t t_first = reverse ? T - 1 : 0;
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
     const bool jok = tile < g.ntiles && j < g.u;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      bias[i][q] = jok ? g.bias[q * g.u + j] : 0.f;
-      rb[i][q] = (RA && jok) ? g.rbias[q * g.u + j] : 0.f;
+      bias[i][q] = jok ? p.bias[q * g.u + j] : 0.f;
+      rb[i][q] = (RA && jok) ? p.rbias[q * g.u + j] : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const bool ok = jok && b0 + 4 * fq + r < (size_t)g.B;
-      hreg[i][r] = (ok && g.h0) ? g.h0[(b0 + 4 * fq + r) * u + j] : 0.f;
-      if (ok && g.training) g.hprev[ro[r] + t_first * u + j] = hreg[i][r];
+      hreg[i][r] = (ok && p.h0) ? p.h0[(b0 + 4 * fq + r) * u + j] : 0.f;
+      if (ok && g.training) p.hprev[ro[r] + t_first * u + j] = hreg[i][r];
     }
   }
   __syncthreads();
 
   for (int s = 0; s < g.T; ++s) {
-    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
-    const size_t e_in = t_in * u, e_out = (size_t)s * u;           // the step's elements at the input time and in processing order
-    const size_t e_next = g.reverse ? e_in - u : e_in + u;          // used only while s + 1 < T
+    const size_t t_in = reverse ? T - 1 - s : (size_t)s;
+    const size_t e_in = t_in * u;                                   // the step's elements at the input time
+    const size_t e_next = reverse ? e_in - u : e_in + u;            // used only while s + 1 < T
+    const bool h_out = g.seq || s == g.T - 1;
+    const size_t h_pos = g.seq ? (size_t)(second ? g.T - 1 - s : s) * g.ld : 0;
     // The lane's row and column guards are formed anew every step from two registers the compiler cannot see through: hoisted out of the loop
     // each of the 5 NT guards would sit in a scalar register pair for the whole sequence, and the four-tile forms would spill scalar registers.
     int lrow = 4 * fq, lcol = fc;
@@ -142,7 +157,7 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
           for (int r = 0; r < 4; ++r) {
             const bool ok = jok && rok[r];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) zv[q][r] = ok ? g.zx[(ro[r] + e_in) * 3 + q * u + j] : 0.f;
+            for (int q = 0; q < 3; ++q) zv[q][r] = ok ? p.zx[(ro[r] + e_in) * 3 + q * u + j] : 0.f;
           }
           f32x4 acc[3];
 #pragma unroll
@@ -160,14 +175,14 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
             if (jok) {
               nxt[(4 * fq + r) * SH + j] = hn;
               if (rok[r]) {
-                g.h[ro[r] + e_out + j] = hn;
+                if (h_out) p.h[(b0 + lrow + r) * h_row + h_pos + j] = hn;
                 if (g.training) {
-                  float* gp = g.gates + (ro[r] + e_in) * 3 + j;
+                  float* gp = p.gates + (ro[r] + e_in) * 3 + j;
                   gp[0] = gz;
                   gp[u] = gr;
                   gp[2 * u] = hh;
-                  g.aux[ro[r] + e_in + j] = qv;
-                  if (s + 1 < g.T) g.hprev[ro[r] + e_next + j] = hn;
+                  p.aux[ro[r] + e_in + j] = qv;
+                  if (s + 1 < g.T) p.hprev[ro[r] + e_next + j] = hn;
                 }
               }
             }
@@ -188,8 +203,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
           for (int r = 0; r < 4; ++r) {
             const bool ok = jok && rok[r];
 #pragma unroll
-            for (int q = 0; q < 2; ++q) zv[q][r] = ok ? g.zx[(ro[r] + e_in) * 3 + q * u + j] : 0.f;
-            ah[i][r] = (ok ? g.zx[(ro[r] + e_in) * 3 + 2 * u + j] : 0.f) + bias[i][2];          // wanted behind the barrier
+            for (int q = 0; q < 2; ++q) zv[q][r] = ok ? p.zx[(ro[r] + e_in) * 3 + q * u + j] : 0.f;
+            ah[i][r] = (ok ? p.zx[(ro[r] + e_in) * 3 + 2 * u + j] : 0.f) + bias[i][2];          // wanted behind the barrier
           }
           f32x4 acc[2];
 #pragma unroll
@@ -204,10 +219,10 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
             if (jok) {
               hs1[(4 * fq + r) * SH + j] = rh;
               if (rok[r] && g.training) {
-                float* gp = g.gates + (ro[r] + e_in) * 3 + j;
+                float* gp = p.gates + (ro[r] + e_in) * 3 + j;
                 gp[0] = gz;
                 gp[u] = gr;
-                g.aux[ro[r] + e_in + j] = rh;
+                p.aux[ro[r] + e_in + j] = rh;
               }
             }
           }
@@ -232,10 +247,10 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
             if (jok) {
               hs0[(4 * fq + r) * SH + j] = hn;
               if (rok[r]) {
-                g.h[ro[r] + e_out + j] = hn;
+                if (h_out) p.h[(b0 + lrow + r) * h_row + h_pos + j] = hn;
                 if (g.training) {
-                  g.gates[(ro[r] + e_in) * 3 + 2 * u + j] = hh;
-                  if (s + 1 < g.T) g.hprev[ro[r] + e_next + j] = hn;
+                  p.gates[(ro[r] + e_in) * 3 + 2 * u + j] = hh;
+                  if (s + 1 < g.T) p.hprev[ro[r] + e_next + j] = hn;
                 }
               }
             }
@@ -247,8 +262,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_fwd_kernel(GruFwdArgs
   }
 }
 
-struct GruBwdArgs {
-  const float* dy;      // (B, T, u) in processing order, or (B, u) for the last step
+struct GruBwdDir {
+  const float* dy;      // dy_seq: (B, T, ld) rows at the positions the forward wrote; else (B, ld) for the last step
   const float* gates;
   const float* hprev;
   const float* aux;     // q, read under reset_after only
@@ -256,7 +271,12 @@ struct GruBwdArgs {
   float* dz;            // (B, T, 3u), input time order: da_z, da_r, da_h
   float* dzr;           // (B, T, 3u): da_z, da_r, dq; reset_after only
   float* dh0;           // (B, u) or NULL
-  int B, T, u, KP, UP, SUT, ntiles, act, ract, reverse, dy_seq;
+};
+
+// blockIdx.y is the direction, as in the forward
+struct GruBwdArgs {
+  GruBwdDir d[2];
+  int B, T, u, KP, UP, SUT, ntiles, act, ract, reverse, dy_seq, ld;
 };
 
 // A (16 rows of LDS, columns [kbeg, kend)) . U^T (rows [kbeg, kend), 16 columns) as one chain from +0: G k groups of 4 a turn, loads first
@@ -278,6 +298,10 @@ __device__ __forceinline__ f32x4 gru_bwd_chain(const float* ap, const float* bp,
 
 template <int NT, bool ULDS, bool RA>
 __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs g) {
+  const bool second = blockIdx.y != 0;
+  const GruBwdDir p = second ? g.d[1] : g.d[0];
+  const bool reverse = second ? !g.reverse : (g.reverse != 0);
+  const size_t dy_row = g.dy_seq ? (size_t)g.T * g.ld : (size_t)g.ld;          // floats between two samples of dy
   extern __shared__ __attribute__((aligned(16))) float gru_lds[];
   const int SD = 3 * g.KP + 1;
   float* dzs = gru_lds;
@@ -289,8 +313,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
 
   for (int e = threadIdx.x; e < LSTM_ROWS * SD; e += blockDim.x) dzs[e] = 0.f;
   if (ULDS)
-    for (int e = threadIdx.x; e < 3 * g.KP * g.SUT; e += blockDim.x) us[e] = g.utp[e];
-  const float* __restrict__ ub = ULDS ? (const float*)us : g.utp;
+    for (int e = threadIdx.x; e < 3 * g.KP * g.SUT; e += blockDim.x) us[e] = p.utp[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : p.utp;
 
   size_t ro[4];                                   // (row T) u of the lane's four rows, as in the forward
   bool rok[4];
@@ -308,8 +332,10 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
   __syncthreads();
 
   for (int s = g.T - 1; s >= 0; --s) {
-    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
-    const size_t e_in = t_in * u, e_out = (size_t)s * u;           // the step's elements at the input time and in processing order
+    const size_t t_in = reverse ? T - 1 - s : (size_t)s;
+    const size_t e_in = t_in * u;                                   // the step's elements at the input time
+    const bool dy_in = g.dy_seq || s == g.T - 1;
+    const size_t dy_pos = g.dy_seq ? (size_t)(second ? g.T - 1 - s : s) * g.ld : 0;
     float daz[NT][4], hpv[NT][4], grv[NT][4];                         // !RA: what the second phase wants of the first
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
@@ -318,24 +344,24 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if (rok[r]) {                                             // rows beyond B keep their +0 in dzs, and a dh of +0
-            const float* gp = g.gates + (ro[r] + e_in) * 3 + j;
+            const float* gp = p.gates + (ro[r] + e_in) * 3 + j;
             const float gz = gp[0], gr = gp[u], hh = gp[2 * u];
-            const float hp = g.hprev[ro[r] + e_in + j];
-            const float dyv = g.dy_seq ? g.dy[ro[r] + e_out + j] : (s == g.T - 1 ? g.dy[(b0 + 4 * fq + r) * u + j] : 0.f);
+            const float hp = p.hprev[ro[r] + e_in + j];
+            const float dyv = dy_in ? p.dy[(b0 + 4 * fq + r) * dy_row + dy_pos + j] : 0.f;
             const float dhv = dyv + dh[i][r];
             const float da_z = (dhv * (hp - hh)) * lstm_act_grad(gz, g.ract);
             const float da_h = (dhv * (1.f - gz)) * lstm_act_grad(hh, g.act);
             dh[i][r] = dhv * gz;
-            float* zp = g.dz + (ro[r] + e_in) * 3 + j;
+            float* zp = p.dz + (ro[r] + e_in) * 3 + j;
             float* ls = dzs + (4 * fq + r) * SD + j;
             zp[0] = da_z;
             zp[2 * u] = da_h;
             if (RA) {
-              const float qv = g.aux[ro[r] + e_in + j];
+              const float qv = p.aux[ro[r] + e_in + j];
               const float da_r = (da_h * qv) * lstm_act_grad(gr, g.ract);
               const float dq = da_h * gr;
               zp[u] = da_r;
-              float* rp = g.dzr + (ro[r] + e_in) * 3 + j;
+              float* rp = p.dzr + (ro[r] + e_in) * 3 + j;
               rp[0] = da_z;
               rp[u] = da_r;
               rp[2 * u] = dq;
@@ -365,7 +391,7 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
               if (rok[r]) {
                 const float da_r = (drh[r] * hpv[i][r]) * lstm_act_grad(grv[i][r], g.ract);
                 dh[i][r] = dh[i][r] + drh[r] * grv[i][r];
-                g.dz[(ro[r] + e_in) * 3 + u + j] = da_r;
+                p.dz[(ro[r] + e_in) * 3 + u + j] = da_r;
                 float* ls = dzs + (4 * fq + r) * SD + j;
                 ls[0] = daz[i][r];
                 ls[g.KP] = da_r;
@@ -390,14 +416,14 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
     if (RA) __syncthreads();  // every wave has left dzs, which step t - 1 overwrites (!RA: see the head of the file)
   }
 
-  if (g.dh0) {
+  if (p.dh0) {
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
       if (tile < g.ntiles && j < g.u) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          if (rok[r]) g.dh0[(b0 + 4 * fq + r) * u + j] = dh[i][r];
+          if (rok[r]) p.dh0[(b0 + 4 * fq + r) * u + j] = dh[i][r];
         }
       }
     }
@@ -405,35 +431,56 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void gru_bwd_kernel(GruBwdArgs
 }
 
 template <int NT, bool ULDS, bool RA>
-void launch_fwd(const GruFwdArgs& a, const GruGeom& m, hipStream_t s) {
+void launch_fwd(const GruFwdArgs& a, const GruGeom& m, int ndir, hipStream_t s) {
   static unsigned long long big = 0;
   allow_big_lds((const void*)gru_fwd_kernel<NT, ULDS, RA>, &big);
-  hipLaunchKernelGGL((gru_fwd_kernel<NT, ULDS, RA>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.fwd_lds_bytes, s, a);
+  hipLaunchKernelGGL((gru_fwd_kernel<NT, ULDS, RA>), dim3(cdiv(a.B, LSTM_ROWS), ndir), dim3(64 * m.nwaves), m.fwd_lds_bytes, s, a);
 }
 
 template <int NT, bool ULDS, bool RA>
-void launch_bwd(const GruBwdArgs& a, const GruGeom& m, hipStream_t s) {
+void launch_bwd(const GruBwdArgs& a, const GruGeom& m, int ndir, hipStream_t s) {
   static unsigned long long big = 0;
   allow_big_lds((const void*)gru_bwd_kernel<NT, ULDS, RA>, &big);
-  hipLaunchKernelGGL((gru_bwd_kernel<NT, ULDS, RA>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
+  hipLaunchKernelGGL((gru_bwd_kernel<NT, ULDS, RA>), dim3(cdiv(a.B, LSTM_ROWS), ndir), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
 }
 
 template <bool RA>
-void pick_fwd(const GruFwdArgs& a, const GruGeom& m, hipStream_t s) {
-  if (m.fwd_u_lds) launch_fwd<1, true, RA>(a, m, s);        // u <= 104: seven tiles at the most, one a wave
-  else if (m.NT == 1) launch_fwd<1, false, RA>(a, m, s);
-  else if (m.NT == 2) launch_fwd<2, false, RA>(a, m, s);
-  else if (m.NT == 3) launch_fwd<3, false, RA>(a, m, s);
-  else launch_fwd<4, false, RA>(a, m, s);
+void pick_fwd(const GruFwdArgs& a, const GruGeom& m, int ndir, hipStream_t s) {
+  if (m.fwd_u_lds) launch_fwd<1, true, RA>(a, m, ndir, s);        // u <= 104: seven tiles at the most, one a wave
+  else if (m.NT == 1) launch_fwd<1, false, RA>(a, m, ndir, s);
+  else if (m.NT == 2) launch_fwd<2, false, RA>(a, m, ndir, s);
+  else if (m.NT == 3) launch_fwd<3, false, RA>(a, m, ndir, s);
+  else launch_fwd<4, false, RA>(a, m, ndir, s);
 }
 
 template <bool RA>
-void pick_bwd(const GruBwdArgs& a, const GruGeom& m, hipStream_t s) {
-  if (m.bwd_u_lds) launch_bwd<1, true, RA>(a, m, s);
-  else if (m.NT == 1) launch_bwd<1, false, RA>(a, m, s);
-  else if (m.NT == 2) launch_bwd<2, false, RA>(a, m, s);
-  else if (m.NT == 3) launch_bwd<3, false, RA>(a, m, s);
-  else launch_bwd<4, false, RA>(a, m, s);
+void pick_bwd(const GruBwdArgs& a, const GruGeom& m, int ndir, hipStream_t s) {
+  if (m.bwd_u_lds) launch_bwd<1, true, RA>(a, m, ndir, s);
+  else if (m.NT == 1) launch_bwd<1, false, RA>(a, m, ndir, s);
+  else if (m.NT == 2) launch_bwd<2, false, RA>(a, m, ndir, s);
+  else if (m.NT == 3) launch_bwd<3, false, RA>(a, m, ndir, s);
+  else launch_bwd<4, false, RA>(a, m, ndir, s);
+}
+
+// pads the U of the ndir directions into the workspace, one copy after the other, and launches the ndir directions as ONE grid
+void run_fwd(GruFwdArgs a, const float* const* U, int ndir, int reset_after, const GruGeom& m, float* ws, hipStream_t s) {
+  for (int d = 0; d < ndir; ++d) {
+    float* up = ws + d * m.fwd_ws_floats;
+    hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U[d], up, a.u, m.KP, m.UP, m.SU, GRU_GATES);
+    a.d[d].up = up;
+  }
+  if (reset_after) pick_fwd<true>(a, m, ndir, s);
+  else pick_fwd<false>(a, m, ndir, s);
+}
+
+void run_bwd(GruBwdArgs a, const float* const* U, int ndir, int reset_after, const GruGeom& m, float* ws, hipStream_t s) {
+  for (int d = 0; d < ndir; ++d) {
+    float* utp = ws + d * m.bwd_ws_floats;
+    hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U[d], utp, a.u, m.KP, m.SUT, GRU_GATES);
+    a.d[d].utp = utp;
+  }
+  if (reset_after) pick_bwd<true>(a, m, ndir, s);
+  else pick_bwd<false>(a, m, ndir, s);
 }
 
 // 0: launch, 1: nothing to do, GN_EINVAL: refused
@@ -470,12 +517,9 @@ int gn_gru_fwd(const float* zx, const float* U, const float* bias, const float* 
     set_error("gru_fwd: workspace too small (%zu bytes, gn_gru_fwd_workspace(%d) = %zu)", ws_bytes, u, m.fwd_ws_floats * sizeof(float));
     return GN_EWORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  float* up = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U, up, u, m.KP, m.UP, m.SU, GRU_GATES);
-  const GruFwdArgs a = {zx, up, bias, rbias, h0, h, gates, hprev, aux, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0};
-  if (reset_after) pick_fwd<true>(a, m, s);
-  else pick_fwd<false>(a, m, s);
+  const GruFwdDir d = {zx, nullptr, bias, rbias, h0, h, gates, hprev, aux};
+  const GruFwdArgs a = {{d, d}, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0, u, 1};
+  run_fwd(a, &U, 1, reset_after, m, (float*)ws, (hipStream_t)stream);
   return check_launch("gru_fwd");
 }
 
@@ -490,13 +534,63 @@ int gn_gru_bwd(const float* dy, const float* gates, const float* hprev, const fl
     set_error("gru_bwd: workspace too small (%zu bytes, gn_gru_bwd_workspace(%d) = %zu)", ws_bytes, u, m.bwd_ws_floats * sizeof(float));
     return GN_EWORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  float* utp = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U, utp, u, m.KP, m.SUT, GRU_GATES);
-  const GruBwdArgs a = {dy, gates, hprev, aux, utp, dz, dzr, dh0, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0};
-  if (reset_after) pick_bwd<true>(a, m, s);
-  else pick_bwd<false>(a, m, s);
+  const GruBwdDir d = {dy, gates, hprev, aux, nullptr, dz, dzr, dh0};
+  const GruBwdArgs a = {{d, d}, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0, u};
+  run_bwd(a, &U, 1, reset_after, m, (float*)ws, (hipStream_t)stream);
   return check_launch("gru_bwd");
+}
+
+int gn_gru_pair_fwd(const float* const* zx, const float* const* U, const float* const* bias, const float* const* rbias, float* const* h, float* const* gates,
+                    float* const* hprev, float* const* aux, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
+                    int reverse0, int seq, int training, void* stream) {
+  const int rc = gru_check("gru_pair_fwd", B, T, u, act, ract, reset_after);
+  if (rc < 0) return rc;
+  GN_REQUIRE(ld >= u, "gru_pair_fwd: ld = %d, a row of h holds at least u = %d floats", ld, u);
+  if (rc) return GN_OK;
+  GN_REQUIRE(zx && U && bias && h && ws, "gru_pair_fwd: null table (zx, U, bias, h and the workspace are required)");
+  GN_REQUIRE(!reset_after || rbias, "gru_pair_fwd: null table (reset_after takes the recurrent biases rbias)");
+  GN_REQUIRE(!training || (gates && hprev && aux), "gru_pair_fwd: null table (the training phase stores gates, hprev and aux)");
+  for (int d = 0; d < 2; ++d) {
+    GN_REQUIRE(zx[d] && U[d] && bias[d] && h[d], "gru_pair_fwd: null pointer in direction %d (zx, U, bias and h are required)", d);
+    GN_REQUIRE(!reset_after || rbias[d], "gru_pair_fwd: null pointer in direction %d (reset_after takes the recurrent bias rbias)", d);
+    GN_REQUIRE(!training || (gates[d] && hprev[d] && aux[d]), "gru_pair_fwd: null pointer in direction %d (the training phase stores gates, hprev and aux)", d);
+  }
+  const GruGeom m = gru_geom(u);
+  if (ws_bytes < 2 * m.fwd_ws_floats * sizeof(float)) {
+    set_error("gru_pair_fwd: workspace too small (%zu bytes, 2 gn_gru_fwd_workspace(%d) = %zu)", ws_bytes, u, 2 * m.fwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  GruFwdArgs a = {{}, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse0 != 0, training != 0, ld, seq != 0};
+  for (int d = 0; d < 2; ++d)
+    a.d[d] = {zx[d], nullptr, bias[d], reset_after ? rbias[d] : nullptr, nullptr, h[d], training ? gates[d] : nullptr, training ? hprev[d] : nullptr,
+              training ? aux[d] : nullptr};
+  run_fwd(a, U, 2, reset_after, m, (float*)ws, (hipStream_t)stream);
+  return check_launch("gru_pair_fwd");
+}
+
+int gn_gru_pair_bwd(const float* const* dy, const float* const* gates, const float* const* hprev, const float* const* aux, const float* const* U,
+                    float* const* dz, float* const* dzr, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
+                    int reverse0, int dy_seq, void* stream) {
+  const int rc = gru_check("gru_pair_bwd", B, T, u, act, ract, reset_after);
+  if (rc < 0) return rc;
+  GN_REQUIRE(ld >= u, "gru_pair_bwd: ld = %d, a row of dy holds at least u = %d floats", ld, u);
+  if (rc) return GN_OK;
+  GN_REQUIRE(dy && gates && hprev && aux && U && dz && ws, "gru_pair_bwd: null table (dy, gates, hprev, aux, U, dz and the workspace are required)");
+  GN_REQUIRE(!reset_after || dzr, "gru_pair_bwd: null table (reset_after writes dzr)");
+  for (int d = 0; d < 2; ++d) {
+    GN_REQUIRE(dy[d] && gates[d] && hprev[d] && aux[d] && U[d] && dz[d],
+               "gru_pair_bwd: null pointer in direction %d (dy, gates, hprev, aux, U and dz are required)", d);
+    GN_REQUIRE(!reset_after || dzr[d], "gru_pair_bwd: null pointer in direction %d (reset_after writes dzr)", d);
+  }
+  const GruGeom m = gru_geom(u);
+  if (ws_bytes < 2 * m.bwd_ws_floats * sizeof(float)) {
+    set_error("gru_pair_bwd: workspace too small (%zu bytes, 2 gn_gru_bwd_workspace(%d) = %zu)", ws_bytes, u, 2 * m.bwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  GruBwdArgs a = {{}, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse0 != 0, dy_seq != 0, ld};
+  for (int d = 0; d < 2; ++d) a.d[d] = {dy[d], gates[d], hprev[d], aux[d], nullptr, dz[d], reset_after ? dzr[d] : nullptr, nullptr};
+  run_bwd(a, U, 2, reset_after, m, (float*)ws, (hipStream_t)stream);
+  return check_launch("gru_pair_bwd");
 }
 
 }  // extern "C"

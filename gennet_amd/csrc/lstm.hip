@@ -33,6 +33,12 @@
 // the h that entered the step at that input time (h0 at the first one).  With them dz lands at the input time index as well, so dW = X^T dz,
 // dU = hprev^T dz and dX = dz W^T are one product each over B T rows whatever the direction.  h itself is written in processing order, as keras
 // returns it.
+//
+// A PAIR OF DIRECTIONS (keras Bidirectional).  The two kernels take a second grid dimension: blockIdx.y is the direction d, which picks
+// its own zx, padded U, bias, stored tensors and h / dy base pointer from the two-entry table of the arguments; direction 0 walks with `reverse`,
+// direction 1 with its negation.  h and dy go through a row stride ld >= u (one (B, T, 2u) buffer at columns 0 and u, or two buffers), direction 0
+// at position s of step s, direction 1 at position T-1-s; with `seq` off only the last processed step is written, into a (B, ld) row buffer.
+// gn_lstm_fwd / gn_lstm_bwd launch one direction with ld = u; gn_lstm_pair_fwd / _bwd launch two, the padded U of both in the workspace.
 #include <math.h>
 
 #include "common.h"
@@ -42,21 +48,30 @@
 namespace gn {
 namespace {
 
-struct LstmFwdArgs {
+struct LstmFwdDir {
   const float* zx;      // (B, T, 4u)
   const float* up;      // padded U: KP rows of SU floats
   const float* bias;    // (4u)
   const float* h0;      // (B, u) or NULL
   const float* c0;
-  float* h;             // (B, T, u), processing order
+  float* h;             // seq: (B, T, ld) rows of which the direction owns u columns; else (B, ld), the last processed step
   float* gates;         // (B, T, 4u), input time order; training only
   float* c;             // (B, T, u)
   float* hprev;         // (B, T, u)
-  int B, T, u, KP, UP, SU, ntiles, act, ract, reverse, training;
+};
+
+// blockIdx.y is the direction: 0 walks with `reverse` and writes step s at position s, 1 walks with !reverse and writes it at position T-1-s
+struct LstmFwdArgs {
+  LstmFwdDir d[2];
+  int B, T, u, KP, UP, SU, ntiles, act, ract, reverse, training, ld, seq;
 };
 
 template <int NT, bool ULDS>
 __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdArgs g) {
+  const bool second = blockIdx.y != 0;
+  const LstmFwdDir p = second ? g.d[1] : g.d[0];
+  const bool reverse = second ? !g.reverse : (g.reverse != 0);
+  const size_t h_row = g.seq ? (size_t)g.T * g.ld : (size_t)g.ld;              // floats between two samples of h
   extern __shared__ __attribute__((aligned(16))) float lstm_lds[];
   const int SH = g.KP + 1;
   float* hs0 = lstm_lds;
@@ -69,36 +84,38 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdAr
 
   for (int e = threadIdx.x; e < LSTM_ROWS * SH; e += blockDim.x) {
     const int row = e / SH, k = e % SH;
-    hs0[e] = (g.h0 && k < g.u && b0 + row < (size_t)g.B) ? g.h0[(b0 + row) * u + k] : 0.f;
+    hs0[e] = (p.h0 && k < g.u && b0 + row < (size_t)g.B) ? p.h0[(b0 + row) * u + k] : 0.f;
     hs1[e] = 0.f;
   }
   if (ULDS)
-    for (int e = threadIdx.x; e < g.KP * g.SU; e += blockDim.x) us[e] = g.up[e];
-  const float* __restrict__ ub = ULDS ? (const float*)us : g.up;
+    for (int e = threadIdx.x; e < g.KP * g.SU; e += blockDim.x) us[e] = p.up[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : p.up;
 
   float creg[NT][4], bias[NT][4];
-  const size_t t_first = g.reverse ? T - 1 : 0;
+  const size_t t_first = reverse ? T - 1 : 0;
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
     const bool jok = tile < g.ntiles && j < g.u;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) bias[i][q] = jok ? g.bias[q * g.u + j] : 0.f;
+    for (int q = 0; q < 4; ++q) bias[i][q] = jok ? p.bias[q * g.u + j] : 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const size_t row = b0 + 4 * fq + r;
       const bool ok = jok && row < (size_t)g.B;
-      creg[i][r] = (ok && g.c0) ? g.c0[row * u + j] : 0.f;
-      if (ok && g.training) g.hprev[(row * T + t_first) * u + j] = g.h0 ? g.h0[row * u + j] : 0.f;
+      creg[i][r] = (ok && p.c0) ? p.c0[row * u + j] : 0.f;
+      if (ok && g.training) p.hprev[(row * T + t_first) * u + j] = p.h0 ? p.h0[row * u + j] : 0.f;
     }
   }
   __syncthreads();
 
   for (int s = 0; s < g.T; ++s) {
-    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
-    const size_t t_next = g.reverse ? t_in - 1 : t_in + 1;          // read only while s + 1 < T
+    const size_t t_in = reverse ? T - 1 - s : (size_t)s;
+    const size_t t_next = reverse ? t_in - 1 : t_in + 1;          // read only while s + 1 < T
     const float* cur = (s & 1) ? hs1 : hs0;
     float* nxt = (s & 1) ? hs0 : hs1;
+    const bool h_out = g.seq || s == g.T - 1;
+    const size_t h_pos = g.seq ? (size_t)(second ? g.T - 1 - s : s) * g.ld : 0;
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int tile = wave + nw * i;
@@ -111,7 +128,7 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdAr
           const size_t row = b0 + 4 * fq + r;
           const bool ok = jok && row < (size_t)g.B;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) zv[q][r] = ok ? g.zx[((row * T + t_in) * 4 + q) * u + j] : 0.f;
+          for (int q = 0; q < 4; ++q) zv[q][r] = ok ? p.zx[((row * T + t_in) * 4 + q) * u + j] : 0.f;
         }
         f32x4 acc[4];
 #pragma unroll
@@ -145,15 +162,15 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdAr
           if (jok) {
             nxt[(4 * fq + r) * SH + j] = hn;
             if (row < (size_t)g.B) {
-              g.h[(row * T + s) * u + j] = hn;
+              if (h_out) p.h[row * h_row + h_pos + j] = hn;
               if (g.training) {
-                float* gp = g.gates + (row * T + t_in) * 4 * u + j;
+                float* gp = p.gates + (row * T + t_in) * 4 * u + j;
                 gp[0] = gi;
                 gp[u] = gf;
                 gp[2 * u] = gg;
                 gp[3 * u] = go;
-                g.c[(row * T + t_in) * u + j] = cn;
-                if (s + 1 < g.T) g.hprev[(row * T + t_next) * u + j] = hn;
+                p.c[(row * T + t_in) * u + j] = cn;
+                if (s + 1 < g.T) p.hprev[(row * T + t_next) * u + j] = hn;
               }
             }
           }
@@ -164,8 +181,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_fwd_kernel(LstmFwdAr
   }
 }
 
-struct LstmBwdArgs {
-  const float* dy;      // (B, T, u) in processing order, or (B, u) for the last step
+struct LstmBwdDir {
+  const float* dy;      // dy_seq: (B, T, ld) rows at the positions the forward wrote; else (B, ld) for the last step
   const float* gates;
   const float* c;
   const float* c0;
@@ -173,11 +190,20 @@ struct LstmBwdArgs {
   float* dz;            // (B, T, 4u), input time order
   float* dh0;           // (B, u) or NULL
   float* dc0;
-  int B, T, u, KP, UP, SUT, ntiles, act, ract, reverse, dy_seq;
+};
+
+// blockIdx.y is the direction, as in the forward
+struct LstmBwdArgs {
+  LstmBwdDir d[2];
+  int B, T, u, KP, UP, SUT, ntiles, act, ract, reverse, dy_seq, ld;
 };
 
 template <int NT, bool ULDS>
 __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdArgs g) {
+  const bool second = blockIdx.y != 0;
+  const LstmBwdDir p = second ? g.d[1] : g.d[0];
+  const bool reverse = second ? !g.reverse : (g.reverse != 0);
+  const size_t dy_row = g.dy_seq ? (size_t)g.T * g.ld : (size_t)g.ld;          // floats between two samples of dy
   extern __shared__ __attribute__((aligned(16))) float lstm_lds[];
   const int SD = 4 * g.KP + 1;
   float* dzs = lstm_lds;
@@ -189,8 +215,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
 
   for (int e = threadIdx.x; e < LSTM_ROWS * SD; e += blockDim.x) dzs[e] = 0.f;
   if (ULDS)
-    for (int e = threadIdx.x; e < 4 * g.KP * g.SUT; e += blockDim.x) us[e] = g.utp[e];
-  const float* __restrict__ ub = ULDS ? (const float*)us : g.utp;
+    for (int e = threadIdx.x; e < 4 * g.KP * g.SUT; e += blockDim.x) us[e] = p.utp[e];
+  const float* __restrict__ ub = ULDS ? (const float*)us : p.utp;
 
   float dh[NT][4], dc[NT][4];
 #pragma unroll
@@ -200,8 +226,10 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
   __syncthreads();
 
   for (int s = g.T - 1; s >= 0; --s) {
-    const size_t t_in = g.reverse ? T - 1 - s : (size_t)s;
-    const size_t t_prev = g.reverse ? t_in + 1 : t_in - 1;          // read only while s > 0
+    const size_t t_in = reverse ? T - 1 - s : (size_t)s;
+    const size_t t_prev = reverse ? t_in + 1 : t_in - 1;          // read only while s > 0
+    const bool dy_in = g.dy_seq || s == g.T - 1;
+    const size_t dy_pos = g.dy_seq ? (size_t)(second ? g.T - 1 - s : s) * g.ld : 0;
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       const int tile = wave + nw * i, j = tile * LSTM_TILE + fc;
@@ -210,11 +238,11 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
         for (int r = 0; r < 4; ++r) {
           const size_t row = b0 + 4 * fq + r;
           if (row < (size_t)g.B) {                                  // rows beyond B keep their +0 in dzs
-            const float* gp = g.gates + (row * T + t_in) * 4 * u + j;
+            const float* gp = p.gates + (row * T + t_in) * 4 * u + j;
             const float gi = gp[0], gf = gp[u], gg = gp[2 * u], go = gp[3 * u];
-            const float cs = g.c[(row * T + t_in) * u + j];
-            const float cp = s > 0 ? g.c[(row * T + t_prev) * u + j] : (g.c0 ? g.c0[row * u + j] : 0.f);
-            const float dyv = g.dy_seq ? g.dy[(row * T + s) * u + j] : (s == g.T - 1 ? g.dy[row * u + j] : 0.f);
+            const float cs = p.c[(row * T + t_in) * u + j];
+            const float cp = s > 0 ? p.c[(row * T + t_prev) * u + j] : (p.c0 ? p.c0[row * u + j] : 0.f);
+            const float dyv = dy_in ? p.dy[row * dy_row + dy_pos + j] : 0.f;
             const float dhv = dyv + dh[i][r];
             const float tc = lstm_act(cs, g.act);
             const float dcv = dc[i][r] + (dhv * go) * lstm_act_grad(tc, g.act);
@@ -223,7 +251,7 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
             const float dzg = (dcv * gi) * lstm_act_grad(gg, g.act);
             const float dzo = (dhv * tc) * lstm_act_grad(go, g.ract);
             dc[i][r] = dcv * gf;
-            float* zp = g.dz + (row * T + t_in) * 4 * u + j;
+            float* zp = p.dz + (row * T + t_in) * 4 * u + j;
             zp[0] = dzi;
             zp[u] = dzf;
             zp[2 * u] = dzg;
@@ -270,8 +298,8 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
       for (int r = 0; r < 4; ++r) {
         const size_t row = b0 + 4 * fq + r;
         if (row < (size_t)g.B) {
-          if (g.dh0) g.dh0[row * u + j] = dh[i][r];
-          if (g.dc0) g.dc0[row * u + j] = dc[i][r];
+          if (p.dh0) p.dh0[row * u + j] = dh[i][r];
+          if (p.dc0) p.dc0[row * u + j] = dc[i][r];
         }
       }
     }
@@ -279,17 +307,44 @@ __global__ __launch_bounds__(64 * LSTM_MAX_WAVES) void lstm_bwd_kernel(LstmBwdAr
 }
 
 template <int NT, bool ULDS>
-void launch_fwd(const LstmFwdArgs& a, const LstmGeom& m, hipStream_t s) {
+void launch_fwd(const LstmFwdArgs& a, const LstmGeom& m, int ndir, hipStream_t s) {
   static unsigned long long big = 0;
   allow_big_lds((const void*)lstm_fwd_kernel<NT, ULDS>, &big);
-  hipLaunchKernelGGL((lstm_fwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.fwd_lds_bytes, s, a);
+  hipLaunchKernelGGL((lstm_fwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS), ndir), dim3(64 * m.nwaves), m.fwd_lds_bytes, s, a);
 }
 
 template <int NT, bool ULDS>
-void launch_bwd(const LstmBwdArgs& a, const LstmGeom& m, hipStream_t s) {
+void launch_bwd(const LstmBwdArgs& a, const LstmGeom& m, int ndir, hipStream_t s) {
   static unsigned long long big = 0;
   allow_big_lds((const void*)lstm_bwd_kernel<NT, ULDS>, &big);
-  hipLaunchKernelGGL((lstm_bwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS)), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
+  hipLaunchKernelGGL((lstm_bwd_kernel<NT, ULDS>), dim3(cdiv(a.B, LSTM_ROWS), ndir), dim3(64 * m.nwaves), m.bwd_lds_bytes, s, a);
+}
+
+// pads the U of the ndir directions into the workspace, one copy after the other, and launches the ndir directions as ONE grid
+void run_fwd(LstmFwdArgs a, const float* const* U, int ndir, const LstmGeom& m, float* ws, hipStream_t s) {
+  for (int d = 0; d < ndir; ++d) {
+    float* up = ws + d * m.fwd_ws_floats;
+    hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U[d], up, a.u, m.KP, m.UP, m.SU, 4);
+    a.d[d].up = up;
+  }
+  if (m.fwd_u_lds) launch_fwd<1, true>(a, m, ndir, s);     // u <= 88: six tiles at the most, one a wave
+  else if (m.NT == 1) launch_fwd<1, false>(a, m, ndir, s);
+  else if (m.NT == 2) launch_fwd<2, false>(a, m, ndir, s);
+  else if (m.NT == 3) launch_fwd<3, false>(a, m, ndir, s);
+  else launch_fwd<4, false>(a, m, ndir, s);
+}
+
+void run_bwd(LstmBwdArgs a, const float* const* U, int ndir, const LstmGeom& m, float* ws, hipStream_t s) {
+  for (int d = 0; d < ndir; ++d) {
+    float* utp = ws + d * m.bwd_ws_floats;
+    hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U[d], utp, a.u, m.KP, m.SUT, 4);
+    a.d[d].utp = utp;
+  }
+  if (m.bwd_u_lds) launch_bwd<1, true>(a, m, ndir, s);     // u <= 80: five tiles at the most, one a wave
+  else if (m.NT == 1) launch_bwd<1, false>(a, m, ndir, s);
+  else if (m.NT == 2) launch_bwd<2, false>(a, m, ndir, s);
+  else if (m.NT == 3) launch_bwd<3, false>(a, m, ndir, s);
+  else launch_bwd<4, false>(a, m, ndir, s);
 }
 
 // 0: launch, 1: nothing to do, GN_EINVAL: refused
@@ -324,15 +379,9 @@ int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float*
     set_error("lstm_fwd: workspace too small (%zu bytes, gn_lstm_fwd_workspace(%d) = %zu)", ws_bytes, u, m.fwd_ws_floats * sizeof(float));
     return GN_EWORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  float* up = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_u_kernel, dim3(stream_grid(m.fwd_ws_floats)), dim3(256), 0, s, U, up, u, m.KP, m.UP, m.SU, 4);
-  const LstmFwdArgs a = {zx, up, bias, h0, c0, h, gates, c, hprev, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0};
-  if (m.fwd_u_lds) launch_fwd<1, true>(a, m, s);           // u <= 88: six tiles at the most, one a wave
-  else if (m.NT == 1) launch_fwd<1, false>(a, m, s);
-  else if (m.NT == 2) launch_fwd<2, false>(a, m, s);
-  else if (m.NT == 3) launch_fwd<3, false>(a, m, s);
-  else launch_fwd<4, false>(a, m, s);
+  const LstmFwdDir d = {zx, nullptr, bias, h0, c0, h, gates, c, hprev};
+  const LstmFwdArgs a = {{d, d}, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse != 0, training != 0, u, 1};
+  run_fwd(a, &U, 1, m, (float*)ws, (hipStream_t)stream);
   return check_launch("lstm_fwd");
 }
 
@@ -346,16 +395,55 @@ int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float
     set_error("lstm_bwd: workspace too small (%zu bytes, gn_lstm_bwd_workspace(%d) = %zu)", ws_bytes, u, m.bwd_ws_floats * sizeof(float));
     return GN_EWORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  float* utp = (float*)ws;
-  hipLaunchKernelGGL(lstm_pad_ut_kernel, dim3(stream_grid(m.bwd_ws_floats)), dim3(256), 0, s, U, utp, u, m.KP, m.SUT, 4);
-  const LstmBwdArgs a = {dy, gates, c, c0, utp, dz, dh0, dc0, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0};
-  if (m.bwd_u_lds) launch_bwd<1, true>(a, m, s);           // u <= 80: five tiles at the most, one a wave
-  else if (m.NT == 1) launch_bwd<1, false>(a, m, s);
-  else if (m.NT == 2) launch_bwd<2, false>(a, m, s);
-  else if (m.NT == 3) launch_bwd<3, false>(a, m, s);
-  else launch_bwd<4, false>(a, m, s);
+  const LstmBwdDir d = {dy, gates, c, c0, nullptr, dz, dh0, dc0};
+  const LstmBwdArgs a = {{d, d}, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse != 0, dy_seq != 0, u};
+  run_bwd(a, &U, 1, m, (float*)ws, (hipStream_t)stream);
   return check_launch("lstm_bwd");
+}
+
+int gn_lstm_pair_fwd(const float* const* zx, const float* const* U, const float* const* bias, float* const* h, float* const* gates, float* const* c,
+                     float* const* hprev, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reverse0, int seq, int training,
+                     void* stream) {
+  const int rc = lstm_check("lstm_pair_fwd", B, T, u, act, ract);
+  if (rc < 0) return rc;
+  GN_REQUIRE(ld >= u, "lstm_pair_fwd: ld = %d, a row of h holds at least u = %d floats", ld, u);
+  if (rc) return GN_OK;
+  GN_REQUIRE(zx && U && bias && h && ws, "lstm_pair_fwd: null table (zx, U, bias, h and the workspace are required)");
+  GN_REQUIRE(!training || (gates && c && hprev), "lstm_pair_fwd: null table (the training phase stores gates, c and hprev)");
+  for (int d = 0; d < 2; ++d) {
+    GN_REQUIRE(zx[d] && U[d] && bias[d] && h[d], "lstm_pair_fwd: null pointer in direction %d (zx, U, bias and h are required)", d);
+    GN_REQUIRE(!training || (gates[d] && c[d] && hprev[d]), "lstm_pair_fwd: null pointer in direction %d (the training phase stores gates, c and hprev)", d);
+  }
+  const LstmGeom m = lstm_geom(u);
+  if (ws_bytes < 2 * m.fwd_ws_floats * sizeof(float)) {
+    set_error("lstm_pair_fwd: workspace too small (%zu bytes, 2 gn_lstm_fwd_workspace(%d) = %zu)", ws_bytes, u, 2 * m.fwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  LstmFwdArgs a = {{}, B, T, u, m.KP, m.UP, m.SU, m.ntiles, act, ract, reverse0 != 0, training != 0, ld, seq != 0};
+  for (int d = 0; d < 2; ++d)
+    a.d[d] = {zx[d], nullptr, bias[d], nullptr, nullptr, h[d], training ? gates[d] : nullptr, training ? c[d] : nullptr, training ? hprev[d] : nullptr};
+  run_fwd(a, U, 2, m, (float*)ws, (hipStream_t)stream);
+  return check_launch("lstm_pair_fwd");
+}
+
+int gn_lstm_pair_bwd(const float* const* dy, const float* const* gates, const float* const* c, const float* const* U, float* const* dz, void* ws,
+                     size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reverse0, int dy_seq, void* stream) {
+  const int rc = lstm_check("lstm_pair_bwd", B, T, u, act, ract);
+  if (rc < 0) return rc;
+  GN_REQUIRE(ld >= u, "lstm_pair_bwd: ld = %d, a row of dy holds at least u = %d floats", ld, u);
+  if (rc) return GN_OK;
+  GN_REQUIRE(dy && gates && c && U && dz && ws, "lstm_pair_bwd: null table (dy, gates, c, U, dz and the workspace are required)");
+  for (int d = 0; d < 2; ++d)
+    GN_REQUIRE(dy[d] && gates[d] && c[d] && U[d] && dz[d], "lstm_pair_bwd: null pointer in direction %d (dy, gates, c, U and dz are required)", d);
+  const LstmGeom m = lstm_geom(u);
+  if (ws_bytes < 2 * m.bwd_ws_floats * sizeof(float)) {
+    set_error("lstm_pair_bwd: workspace too small (%zu bytes, 2 gn_lstm_bwd_workspace(%d) = %zu)", ws_bytes, u, 2 * m.bwd_ws_floats * sizeof(float));
+    return GN_EWORKSPACE;
+  }
+  LstmBwdArgs a = {{}, B, T, u, m.KP, m.UP, m.SUT, m.ntiles, act, ract, reverse0 != 0, dy_seq != 0, ld};
+  for (int d = 0; d < 2; ++d) a.d[d] = {dy[d], gates[d], c[d], nullptr, nullptr, dz[d], nullptr, nullptr};
+  run_bwd(a, U, 2, m, (float*)ws, (hipStream_t)stream);
+  return check_launch("lstm_pair_bwd");
 }
 
 }  // extern "C"

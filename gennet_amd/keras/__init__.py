@@ -12,6 +12,7 @@
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, Dot, add, dot, ...                   # all eight merge layers and functions
     from gennet_amd.keras.layers.recurrent import LSTM, GRU            # also gennet_amd.keras.layers.LSTM, .GRU
+    from gennet_amd.keras.layers.wrappers import Bidirectional         # also gennet_amd.keras.layers.Bidirectional: over LSTM or GRU
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -71,10 +72,11 @@ _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate', 'Dot',
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
 _recurrent = _pick(_layers, 'LSTM', 'GRU')
+_wrappers = _pick(_layers, 'Bidirectional')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))
-for _d in (_core, _norm, _conv, _act, _noise, _merge, _recurrent):
+for _d in (_core, _norm, _conv, _act, _noise, _merge, _recurrent, _wrappers):
     _top.update((k, v) for k, v in _d.items() if v is _layers.__dict__.get(k))
 
 _TREE = {
@@ -93,6 +95,7 @@ _TREE = {
     'layers.pooling': _pooling,
     'layers.merge': _merge,
     'layers.recurrent': _recurrent,
+    'layers.wrappers': _wrappers,
     'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
     'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }

@@ -242,6 +242,8 @@ def layer_config(layer):
             cfg.update(unit_forget_bias=layer.unit_forget_bias)
         else:
             cfg.update(reset_after=layer.reset_after)
+    elif isinstance(layer, L.Bidirectional):     # keras 2.2.4 layers/wrappers.py: Wrapper.get_config's 'layer' entry and merge_mode
+        cfg.update(layer={'class_name': layer.layer.__class__.__name__, 'config': layer_config(layer.layer)}, merge_mode=layer.merge_mode)
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -369,6 +371,11 @@ def _layer_from_config(class_name, cfg, custom_objects):
                 'bias_constraint', 'dropout', 'recurrent_dropout', 'implementation', 'return_sequences', 'return_state', 'go_backwards', 'stateful',
                 'unroll')
         return getattr(L, class_name)(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
+    if class_name == 'Bidirectional':            # the inner layer through the LSTM / GRU path above, with its own name and go_backwards
+        inner = cfg['layer']
+        if inner['class_name'] not in ('LSTM', 'GRU'):
+            raise ValueError('Bidirectional wraps an LSTM or a GRU, not %s' % inner['class_name'])
+        return L.Bidirectional(_layer_from_config(inner['class_name'], inner['config'], None), merge_mode=cfg.get('merge_mode', 'concat'), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 

@@ -629,6 +629,120 @@ def gru_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activation='h
     return dz, dzr, dh0
 
 
+# ------------------------------------------------------------------ a pair of directions in one launch (keras Bidirectional)
+def _pair(what, ts):
+    ts = list(ts)
+    if len(ts) != 2:
+        raise ValueError('%s: one tensor a direction is expected, got %d' % (what, len(ts)))
+    return ts
+
+
+def _pair_out(B, T, u, concat, seq, device):
+    """(the two h or dy views of a pair launch, ld, the merged buffer or None): concat: ONE (B, [T,] 2u) buffer the directions address at columns 0
+    and u with ld = 2u; else two (B, [T,] u) buffers with ld = u."""
+    lead = (B, T) if seq else (B,)
+    if concat:
+        y = torch.empty(lead + (2 * u,), dtype=torch.float32, device=device)
+        return [y[..., :u], y[..., u:]], 2 * u, y
+    return [torch.empty(lead + (u,), dtype=torch.float32, device=device) for _ in range(2)], u, None
+
+
+def _pair_dy(what, dy, B, T, u, concat):
+    """(the two dy views, ld, dy_seq) of a pair backward.  concat: dy is ONE (B, [T,] 2u) tensor, read at columns 0 and u with ld = 2u; else a
+    list of two (B, [T,] u) tensors (which may be one tensor twice), ld = u.  dy_seq: whether dy carries the T axis."""
+    if concat:
+        if not torch.is_tensor(dy):
+            raise ValueError('%s: concat=True takes the one concatenated dy, (B, T, 2u) or (B, 2u), not a list' % what)
+        _chk(dy)
+        if tuple(dy.shape) not in ((B, T, 2 * u), (B, 2 * u)):
+            raise ValueError('%s: the concatenated dy is (B, T, 2u) or (B, 2u), got %r' % (what, tuple(dy.shape)))
+        return [dy[..., :u], dy[..., u:]], 2 * u, dy.dim() == 3
+    if torch.is_tensor(dy):
+        raise ValueError('%s: concat=False takes one dy a direction, a list of two (B, T, u) or (B, u) tensors' % what)
+    dy = _pair(what, dy)
+    _chk(*dy)
+    if tuple(dy[0].shape) not in ((B, T, u), (B, u)) or dy[1].shape != dy[0].shape:
+        raise ValueError('%s: each dy is (B, T, u) or (B, u), got %r and %r' % (what, tuple(dy[0].shape), tuple(dy[1].shape)))
+    return dy, u, dy[0].dim() == 3
+
+
+def lstm_pair_fwd(zx, U, bias, activation='tanh', recurrent_activation='hard_sigmoid', reverse0=False, seq=True, concat=True, training=False):
+    """Two LSTM directions over zx[d] (B, T, 4u) in ONE launch; direction 0 walks with reverse0, direction 1 with its negation, and direction 1's
+    step s lands at position T-1-s.  -> (y, h, gates, c, hprev): concat: y is the (B, [T,] 2u) output both directions wrote and h its two column
+    views; else y is None and h two (B, [T,] u) tensors.  gates, c, hprev: lists of two as lstm_fwd stores them, or None outside the training
+    phase.  seq False: only the last processed step of each direction."""
+    zx, U, bias = _pair('lstm_pair_fwd', zx), _pair('lstm_pair_fwd', U), _pair('lstm_pair_fwd', bias)
+    _chk(*(zx + U + bias))
+    B, T, u = _lstm_shape('lstm_pair_fwd', zx[0], U[0])
+    assert (B, T, u) == _lstm_shape('lstm_pair_fwd', zx[1], U[1]) and all(b.numel() == 4 * u for b in bias)
+    dev = zx[0].device
+    h, ld, y = _pair_out(B, T, u, concat, seq, dev)
+    gates = c = hprev = None
+    if training:
+        gates = [torch.empty((B, T, 4 * u), dtype=torch.float32, device=dev) for _ in range(2)]
+        c, hprev = ([torch.empty((B, T, u), dtype=torch.float32, device=dev) for _ in range(2)] for _ in range(2))
+    ws = workspace(2 * _lib.size('gn_lstm_fwd_workspace', u), dev)
+    _lib.call('gn_lstm_pair_fwd', _ptr_table(zx), _ptr_table(U), _ptr_table(bias), _ptr_table(h), _ptr_table(gates or [None, None]),
+              _ptr_table(c or [None, None]), _ptr_table(hprev or [None, None]), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation],
+              LSTM_ACT[recurrent_activation], int(bool(reverse0)), int(bool(seq)), int(bool(training)), _stream())
+    return y, h, gates, c, hprev
+
+
+def lstm_pair_bwd(dy, gates, c, U, activation='tanh', recurrent_activation='hard_sigmoid', reverse0=False, concat=True):
+    """Backward through time of both directions in ONE launch.  concat: dy is the concatenated (B, [T,] 2u) gradient, read through ld = 2u;
+    else a list of two (B, [T,] u) tensors (the same tensor twice where the merge hands both directions one gradient).  -> [dz_0, dz_1], each (B, T, 4u) at the
+    input time index."""
+    gates, c, U = _pair('lstm_pair_bwd', gates), _pair('lstm_pair_bwd', c), _pair('lstm_pair_bwd', U)
+    _chk(*(gates + c + U))
+    B, T, u = _lstm_shape('lstm_pair_bwd', gates[0], U[0])
+    assert (B, T, u) == _lstm_shape('lstm_pair_bwd', gates[1], U[1]) and all(tuple(t.shape) == (B, T, u) for t in c)
+    dys, ld, dy_seq = _pair_dy('lstm_pair_bwd', dy, B, T, u, concat)
+    dz = [torch.empty_like(g) for g in gates]
+    ws = workspace(2 * _lib.size('gn_lstm_bwd_workspace', u), dz[0].device)
+    _lib.call('gn_lstm_pair_bwd', _ptr_table(dys), _ptr_table(gates), _ptr_table(c), _ptr_table(U), _ptr_table(dz), _p(ws), ws.numel(), B, T, u, ld,
+              LSTM_ACT[activation], LSTM_ACT[recurrent_activation], int(bool(reverse0)), int(dy_seq), _stream())
+    return dz
+
+
+def gru_pair_fwd(zx, U, bias, rbias=None, activation='tanh', recurrent_activation='hard_sigmoid', reset_after=False, reverse0=False, seq=True,
+                 concat=True, training=False):
+    """lstm_pair_fwd for the GRU: -> (y, h, gates, hprev, aux).  rbias: the two recurrent biases, exactly under reset_after."""
+    zx, U, bias = _pair('gru_pair_fwd', zx), _pair('gru_pair_fwd', U), _pair('gru_pair_fwd', bias)
+    if (rbias is not None) != bool(reset_after):
+        raise ValueError('gru_pair_fwd: the recurrent biases go with reset_after, and only with it')
+    rbias = _pair('gru_pair_fwd', rbias) if reset_after else [None, None]
+    _chk(*(zx + U + bias + rbias))
+    B, T, u = _gru_shape('gru_pair_fwd', zx[0], U[0])
+    assert (B, T, u) == _gru_shape('gru_pair_fwd', zx[1], U[1]) and all(b is None or b.numel() == 3 * u for b in bias + rbias)
+    dev = zx[0].device
+    h, ld, y = _pair_out(B, T, u, concat, seq, dev)
+    gates = hprev = aux = None
+    if training:
+        gates = [torch.empty((B, T, 3 * u), dtype=torch.float32, device=dev) for _ in range(2)]
+        hprev, aux = ([torch.empty((B, T, u), dtype=torch.float32, device=dev) for _ in range(2)] for _ in range(2))
+    ws = workspace(2 * _lib.size('gn_gru_fwd_workspace', u), dev)
+    _lib.call('gn_gru_pair_fwd', _ptr_table(zx), _ptr_table(U), _ptr_table(bias), _ptr_table(rbias), _ptr_table(h), _ptr_table(gates or [None, None]),
+              _ptr_table(hprev or [None, None]), _ptr_table(aux or [None, None]), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation],
+              LSTM_ACT[recurrent_activation], int(bool(reset_after)), int(bool(reverse0)), int(bool(seq)), int(bool(training)), _stream())
+    return y, h, gates, hprev, aux
+
+
+def gru_pair_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activation='hard_sigmoid', reset_after=False, reverse0=False, concat=True):
+    """lstm_pair_bwd for the GRU: -> ([dz_0, dz_1], [dzr_0, dzr_1] under reset_after, else None), as gru_bwd forms them."""
+    gates, hprev, aux, U = (_pair('gru_pair_bwd', t) for t in (gates, hprev, aux, U))
+    _chk(*(gates + hprev + aux + U))
+    B, T, u = _gru_shape('gru_pair_bwd', gates[0], U[0])
+    assert (B, T, u) == _gru_shape('gru_pair_bwd', gates[1], U[1]) and all(tuple(t.shape) == (B, T, u) for t in hprev + aux)
+    dys, ld, dy_seq = _pair_dy('gru_pair_bwd', dy, B, T, u, concat)
+    dz = [torch.empty_like(g) for g in gates]
+    dzr = [torch.empty_like(g) for g in gates] if reset_after else None
+    ws = workspace(2 * _lib.size('gn_gru_bwd_workspace', u), dz[0].device)
+    _lib.call('gn_gru_pair_bwd', _ptr_table(dys), _ptr_table(gates), _ptr_table(hprev), _ptr_table(aux), _ptr_table(U), _ptr_table(dz),
+              _ptr_table(dzr or [None, None]), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation], LSTM_ACT[recurrent_activation],
+              int(bool(reset_after)), int(bool(reverse0)), int(dy_seq), _stream())
+    return dz, dzr
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

@@ -1,5 +1,5 @@
 """keras.layers.LSTM and keras.layers.GRU (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrences of csrc/lstm.hip and
-csrc/gru.hip; DESIGN 8o, 8p.
+csrc/gru.hip; DESIGN 8o, 8p.  keras.layers.Bidirectional (layers/wrappers.py) over either: both directions in one launch; DESIGN 8q.
 
 The classes are part of the gennet_amd.layers name space (gennet_amd.layers.LSTM is this LSTM), as every layer is."""
 import numpy as np
@@ -98,6 +98,22 @@ def _init_recurrent(layer, what, kw, units, activation, recurrent_activation, us
     layer.implementation, layer.unroll = int(implementation), bool(unroll)
 
 
+def _add_triple(owner, cell, prefix, Cin):
+    """kernel (Cin, G u), recurrent_kernel (u, G u) and bias of `cell` (an LSTM or a GRU) as Params of `owner` under `prefix`, drawn in keras'
+    order from the generator glorot_uniform draws from, each with the cell's regularizer"""
+    u, G = cell.units, cell.n_gates
+    return (owner.add_weight(prefix + 'kernel', engine.glorot_uniform((Cin, G * u)), regularizer=cell.kernel_regularizer),
+            owner.add_weight(prefix + 'recurrent_kernel', orthogonal_blocks(u, G), regularizer=cell.recurrent_regularizer),
+            owner.add_weight(prefix + 'bias', cell.initial_bias(), regularizer=cell.bias_regularizer))
+
+
+def _input_grad(dz, kernel, x_shape):
+    """dX = dz . W^T over the B T rows"""
+    B, T, Cin = x_shape
+    G = dz.shape[2]
+    return ops.bmm(dz.view(1, B * T, G), kernel.data.view(1, Cin, G), trans_b=True).view(B, T, Cin)
+
+
 class GRU(Layer):
     """keras.layers.GRU(units): (B, T, Cin) -> (B, units), or (B, T, units) with return_sequences.  GRUCell of keras 2.2.4, gate columns z, r, h
     in kernel (Cin, 3u), recurrent_kernel (u, 3u) and bias (3u), or (2, 3u) under reset_after (row 0 the input bias b, row 1 the recurrent rb):
@@ -128,9 +144,12 @@ class GRU(Layer):
         Cin, u = int(input_shape[1]), self.units
         if u > 512:
             raise NotImplementedError('%s: GRU(units=%d): at most 512 units run (a block carries all units of its samples on chip)' % (self.name, u))
-        self.kernel = self.add_weight('kernel', engine.glorot_uniform((Cin, 3 * u)), regularizer=self.kernel_regularizer)
-        self.recurrent_kernel = self.add_weight('recurrent_kernel', orthogonal_blocks(u, 3), regularizer=self.recurrent_regularizer)
-        self.bias = self.add_weight('bias', np.zeros((2, 3 * u) if self.reset_after else (3 * u,), np.float32), regularizer=self.bias_regularizer)
+        self.kernel, self.recurrent_kernel, self.bias = _add_triple(self, self, '', Cin)
+
+    n_gates = 3
+
+    def initial_bias(self):
+        return np.zeros((2, 3 * self.units) if self.reset_after else (3 * self.units,), np.float32)
 
     def compute_output_shape(self, input_shape):
         return (int(input_shape[0]), self.units) if self.return_sequences else (self.units,)
@@ -149,28 +168,33 @@ class GRU(Layer):
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
         x, hprev, gates, aux = ctx.tape.pop(node.index)
-        B, T, Cin = x.shape
+        B, T, _ = x.shape
         u = self.units
         dz, dzr, _ = ops.gru_bwd(dy.contiguous().view((B, T, u) if self.return_sequences else (B, u)), gates, hprev, aux, self.recurrent_kernel.data,
                                  self.activation, self.recurrent_activation, reset_after=self.reset_after, reverse=self.go_backwards)
-        dz2 = dz.view(B * T, 3 * u)
         if need_dw:
-            rows_product(x.view(B * T, Cin), dz2, self.kernel.grad)
-            db = self.bias.grad.view(-1, 3 * u)
-            ops.bias_grad(dz2, db[0])
-            if self.reset_after:
-                dzr2 = dzr.view(B * T, 3 * u)
-                rows_product(hprev.view(B * T, u), dzr2, self.recurrent_kernel.grad)
-                ops.bias_grad(dzr2, db[1])
-            else:
-                dzr_zr, dz_h = ops.concat_bwd(dz2, [(B * T, 2 * u), (B * T, u)], 1)
-                dU_zr, dU_h = dz.new_empty((u, 2 * u)), dz.new_empty((u, u))
-                rows_product(hprev.view(B * T, u), dzr_zr, dU_zr)
-                rows_product(aux.view(B * T, u), dz_h, dU_h)
-                ops.concat_fwd([dU_zr, dU_h], 1, out=self.recurrent_kernel.grad)
-        if not need_dx:
-            return None
-        return ops.bmm(dz2.view(1, B * T, 3 * u), self.kernel.data.view(1, Cin, 3 * u), trans_b=True).view(B, T, Cin)
+            self.weight_grads(x, (hprev, gates, aux), dz, dzr, self.kernel, self.recurrent_kernel, self.bias)
+        return _input_grad(dz, self.kernel, x.shape) if need_dx else None
+
+    def weight_grads(self, x, kept, dz, dzr, kernel, recurrent_kernel, bias):
+        """the gradients of one direction's three weights from what its recurrence stored (kept = hprev, gates, aux) and its backward wrote"""
+        hprev, _, aux = kept
+        B, T, Cin = x.shape
+        u = self.units
+        dz2 = dz.view(B * T, 3 * u)
+        rows_product(x.view(B * T, Cin), dz2, kernel.grad)
+        db = bias.grad.view(-1, 3 * u)
+        ops.bias_grad(dz2, db[0])
+        if self.reset_after:
+            dzr2 = dzr.view(B * T, 3 * u)
+            rows_product(hprev.view(B * T, u), dzr2, recurrent_kernel.grad)
+            ops.bias_grad(dzr2, db[1])
+        else:
+            dzr_zr, dz_h = ops.concat_bwd(dz2, [(B * T, 2 * u), (B * T, u)], 1)
+            dU_zr, dU_h = dz.new_empty((u, 2 * u)), dz.new_empty((u, u))
+            rows_product(hprev.view(B * T, u), dzr_zr, dU_zr)
+            rows_product(aux.view(B * T, u), dz_h, dU_h)
+            ops.concat_fwd([dU_zr, dU_h], 1, out=recurrent_kernel.grad)
 
 
 class LSTM(Layer):
@@ -201,12 +225,16 @@ class LSTM(Layer):
         Cin, u = int(input_shape[1]), self.units
         if u > 512:
             raise NotImplementedError('%s: LSTM(units=%d): at most 512 units run (a block carries all units of its samples on chip)' % (self.name, u))
-        self.kernel = self.add_weight('kernel', engine.glorot_uniform((Cin, 4 * u)), regularizer=self.kernel_regularizer)
-        self.recurrent_kernel = self.add_weight('recurrent_kernel', orthogonal_blocks(u), regularizer=self.recurrent_regularizer)
+        self.kernel, self.recurrent_kernel, self.bias = _add_triple(self, self, '', Cin)
+
+    n_gates = 4
+
+    def initial_bias(self):
+        u = self.units
         bias = np.zeros(4 * u, np.float32)
         if self.unit_forget_bias:
             bias[u:2 * u] = 1.0
-        self.bias = self.add_weight('bias', bias, regularizer=self.bias_regularizer)
+        return bias
 
     def compute_output_shape(self, input_shape):
         return (int(input_shape[0]), self.units) if self.return_sequences else (self.units,)
@@ -224,15 +252,114 @@ class LSTM(Layer):
 
     def backward(self, ctx, node, dy, need_dx, need_dw):
         x, hprev, gates, c = ctx.tape.pop(node.index)
-        B, T, Cin = x.shape
+        B, T, _ = x.shape
         u = self.units
         dz, _, _ = ops.lstm_bwd(dy.contiguous().view((B, T, u) if self.return_sequences else (B, u)), gates, c, self.recurrent_kernel.data, None,
                                 self.activation, self.recurrent_activation, reverse=self.go_backwards)
-        dz2 = dz.view(B * T, 4 * u)
         if need_dw:
-            rows_product(x.view(B * T, Cin), dz2, self.kernel.grad)
-            rows_product(hprev.view(B * T, u), dz2, self.recurrent_kernel.grad)
-            ops.bias_grad(dz2, self.bias.grad)
+            self.weight_grads(x, (hprev, gates, c), dz, None, self.kernel, self.recurrent_kernel, self.bias)
+        return _input_grad(dz, self.kernel, x.shape) if need_dx else None
+
+    def weight_grads(self, x, kept, dz, dzr, kernel, recurrent_kernel, bias):
+        """the gradients of one direction's three weights from what its recurrence stored (kept = hprev, gates, c) and its backward wrote"""
+        B, T, Cin = x.shape
+        dz2 = dz.view(B * T, 4 * self.units)
+        rows_product(x.view(B * T, Cin), dz2, kernel.grad)
+        rows_product(kept[0].view(B * T, self.units), dz2, recurrent_kernel.grad)
+        ops.bias_grad(dz2, bias.grad)
+
+
+_MERGE_PASS = {'sum': 'add', 'mul': 'mul', 'ave': 'avg'}          # merge_mode -> the mode of ops.merge_fwd
+
+
+class Bidirectional(Layer):
+    """keras.layers.Bidirectional(layer, merge_mode='concat') (keras 2.2.4 layers/wrappers.py) over an unbuilt LSTM or GRU of this module:
+    (B, T, Cin) -> (B, [T,] 2u) for 'concat', (B, [T,] u) for 'sum', 'mul' and 'ave'.  The forward copy walks as the inner layer's go_backwards
+    says, the backward copy the other way, and with return_sequences the backward copy's sequence is turned round (K.reverse along time)
+    before the halves are merged.  Six weights in keras' order: <name>/forward_<inner>/{kernel, recurrent_kernel, bias}, then the same under
+    backward_<inner>; each carries the inner layer's regularizer, and the forward triple is drawn first (what a lone inner layer draws).
+    Forward: zx_d = X . W_d, two gn_bmm; then ONE pair launch (ops.lstm_pair_fwd / gru_pair_fwd: the direction is the grid's second dimension)
+    that writes both halves in time-aligned order -- for 'concat' straight into the (B, [T,] 2u) output, so no reverse and no concatenate pass
+    exists; for the other modes into two buffers that ops.merge_fwd joins.
+    Backward: 'concat' and 'sum' hand dy to the pair launch as it is (read through a row stride), 'ave' one ops.scale by 1/2 shared by both
+    directions, 'mul' the two ops.merge_bwd; ONE pair launch; the weight gradients a direction as LSTM.backward / GRU.backward form them
+    (weight_grads); dX = dz_f . W_f^T + dz_b . W_b^T, two gn_bmm and one add pass, forward term first.  Fixed order, no atomics.  The tape keeps
+    x and both directions' stored tensors (and the two halves under 'mul'), in the training phase only.  The planner fuses nothing onto the
+    layer, and dy is not written."""
+
+    def __init__(self, layer, merge_mode='concat', **kw):
+        if not isinstance(layer, (LSTM, GRU)):
+            raise ValueError('Please initialize `Bidirectional` layer with an unbuilt `LSTM` or `GRU` instance. You passed: %r' % (layer,))
+        if layer.built:
+            raise ValueError('Bidirectional(layer=%s): the inner layer is already built; the wrapper owns both copies of its weights' % layer.name)
+        if merge_mode is None:
+            raise NotImplementedError('Bidirectional(merge_mode=None): the two halves as two outputs are not implemented (a layer has one output)')
+        if merge_mode not in ('concat', 'sum', 'mul', 'ave'):
+            raise ValueError('Invalid merge mode. Merge mode should be one of {"sum", "mul", "ave", "concat"}, got %r' % (merge_mode,))
+        if kw.pop('weights', None) is not None:
+            raise NotImplementedError('Bidirectional(weights=...): initial weights through the constructor are not implemented; use set_weights')
+        if layer.activity_regularizer is not None:
+            raise NotImplementedError('Bidirectional(layer=%s(activity_regularizer=...)): an activity regularizer on the inner layer is not '
+                                      'implemented' % type(layer).__name__)
+        Layer.__init__(self, **kw)
+        self.layer, self.merge_mode = layer, merge_mode
+
+    def build(self, input_shape):
+        inner = self.layer
+        if len(input_shape) != 2:
+            raise ValueError('%s (Bidirectional) expects (batch, timesteps, features), got %r' % (self.name, (None,) + tuple(input_shape)))
+        if inner.units > 512:
+            raise NotImplementedError('%s: %s(units=%d): at most 512 units run (a block carries all units of its samples on chip)'
+                                      % (self.name, type(inner).__name__, inner.units))
+        Cin = int(input_shape[1])
+        self.forward_weights = _add_triple(self, inner, 'forward_%s/' % inner.name, Cin)
+        self.backward_weights = _add_triple(self, inner, 'backward_%s/' % inner.name, Cin)
+
+    def compute_output_shape(self, input_shape):
+        width = self.layer.units * (2 if self.merge_mode == 'concat' else 1)
+        return (int(input_shape[0]), width) if self.layer.return_sequences else (width,)
+
+    def forward(self, ctx, node, x):
+        inner = self.layer
+        x = x.contiguous()
+        B, T, Cin = x.shape
+        G = inner.n_gates * inner.units
+        triples = (self.forward_weights, self.backward_weights)
+        zx = [ops.bmm(x.view(1, B * T, Cin), W.data.view(1, Cin, G)).view(B, T, G) for W, _, _ in triples]
+        U = [t[1].data for t in triples]
+        kw = dict(activation=inner.activation, recurrent_activation=inner.recurrent_activation, reverse0=inner.go_backwards,
+                  seq=inner.return_sequences, concat=self.merge_mode == 'concat', training=ctx.training)
+        if isinstance(inner, LSTM):
+            y, h, gates, last, hprev = ops.lstm_pair_fwd(zx, U, [t[2].data for t in triples], **kw)                 # last: c
+        else:
+            b2 = [t[2].data.view(-1, G) for t in triples]
+            y, h, gates, hprev, last = ops.gru_pair_fwd(zx, U, [b[0] for b in b2], [b[1] for b in b2] if inner.reset_after else None,
+                                                        reset_after=inner.reset_after, **kw)                      # last: aux
+        if ctx.training:
+            ctx.tape[node.index] = (x, hprev, gates, last, h if self.merge_mode == 'mul' else None)
+        return y if self.merge_mode == 'concat' else ops.merge_fwd(_MERGE_PASS[self.merge_mode], h)
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        inner = self.layer
+        x, hprev, gates, last, h = ctx.tape.pop(node.index)
+        dy = dy.contiguous().view((x.shape[0],) + tuple(node.out_shape))
+        if self.merge_mode == 'mul':
+            dy = [ops.merge_bwd('mul', dy, h, d) for d in range(2)]
+        elif self.merge_mode == 'ave':
+            dy = [ops.scale(dy, 0.5)] * 2
+        elif self.merge_mode == 'sum':
+            dy = [dy, dy]
+        triples = (self.forward_weights, self.backward_weights)
+        U = [t[1].data for t in triples]
+        kw = dict(activation=inner.activation, recurrent_activation=inner.recurrent_activation, reverse0=inner.go_backwards,
+                  concat=self.merge_mode == 'concat')
+        if isinstance(inner, LSTM):
+            dz, dzr = ops.lstm_pair_bwd(dy, gates, last, U, **kw), None
+        else:
+            dz, dzr = ops.gru_pair_bwd(dy, gates, hprev, last, U, reset_after=inner.reset_after, **kw)
+        if need_dw:
+            for d, (W, Ud, b) in enumerate(triples):
+                inner.weight_grads(x, (hprev[d], gates[d], last[d]), dz[d], dzr[d] if dzr else None, W, Ud, b)
         if not need_dx:
             return None
-        return ops.bmm(dz2.view(1, B * T, 4 * u), self.kernel.data.view(1, Cin, 4 * u), trans_b=True).view(B, T, Cin)
+        return ops.merge_fwd('add', [_input_grad(dz[d], triples[d][0], x.shape) for d in range(2)])

@@ -446,6 +446,25 @@ int gn_lstm_fwd(const float* zx, const float* U, const float* bias, const float*
 int gn_lstm_bwd(const float* dy, const float* gates, const float* c, const float* c0, const float* U, float* dz, float* dh0, float* dc0, void* ws,
                 size_t ws_bytes, int B, int T, int u, int act, int ract, int reverse, int dy_seq, void* stream);
 
+/* ---- a PAIR of LSTM directions in one launch (csrc/lstm.hip; keras layers.Bidirectional).  The kernels are gn_lstm_fwd's and
+ * gn_lstm_bwd's with a second grid dimension: blockIdx.y is the direction d, the grid is ceil(B / 16) x 2 blocks, and no block waits on another.
+ * Every per-direction operand comes as a HOST table of two device pointers.  Direction 0 walks with reverse = reverse0, direction 1 with
+ * !reverse0; each direction is bit for bit what the single entry point gives on the same operands.  No initial state (h0 = c0 = 0).
+ * h / dy are addressed through a row stride `ld` >= u in floats and the direction's base pointer: two (B, T, u) buffers with ld = u, or ONE
+ *   (B, T, 2u) buffer with h[1] = h[0] + u and ld = 2u (the concatenated output; the directions own disjoint columns).  Direction 0 writes step
+ *   s at position s, direction 1 at position T-1-s (keras' K.reverse of the backward half: by position, whatever reverse0 is).  seq == 0: only
+ *   the last processed step of each direction is written, into a (B, ld) row buffer; dy_seq == 0: dy is that (B, ld) buffer.
+ * zx, U, bias, gates, c, hprev, dz: per direction, contiguous, at the input time index, as in gn_lstm_fwd / gn_lstm_bwd.  gates, c and hprev
+ *   (the tables, or their entries) may be NULL without `training`.
+ * ws: TWICE gn_lstm_fwd_workspace(u) / gn_lstm_bwd_workspace(u) bytes: the padded U (U^T) of direction 0, then of direction 1.
+ * GN_EINVAL, nothing launched: a NULL table or entry, ld < u, T < 1, u < 1 or u > 512, B < 0, an unknown activation code; GN_EWORKSPACE: ws too
+ * small.  B == 0 is GN_OK without a launch. */
+int gn_lstm_pair_fwd(const float* const* zx, const float* const* U, const float* const* bias, float* const* h, float* const* gates, float* const* c,
+                     float* const* hprev, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reverse0, int seq, int training,
+                     void* stream);
+int gn_lstm_pair_bwd(const float* const* dy, const float* const* gates, const float* const* c, const float* const* U, float* const* dz, void* ws,
+                     size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reverse0, int dy_seq, void* stream);
+
 /* ---- GRU recurrence (csrc/gru.hip; keras layers.GRU, GRUCell of keras 2.2.4, both reset_after forms).  Gate columns z, r, h of width u:
  *   a_t = zx_t + b;  reset_after 0: m = h_{t-1} . U[:, :2u], z = ra(a_z + m_z), r = ra(a_r + m_r), hh = act(a_h + (r h_{t-1}) . U_h)
  *                    reset_after 1: m = h_{t-1} . U + rb,    z = ra(a_z + m_z), r = ra(a_r + m_r), q = m_h, hh = act(a_h + r q)
@@ -471,6 +490,23 @@ int gn_gru_fwd(const float* zx, const float* U, const float* bias, const float* 
                void* ws, size_t ws_bytes, int B, int T, int u, int act, int ract, int reset_after, int reverse, int training, void* stream);
 int gn_gru_bwd(const float* dy, const float* gates, const float* hprev, const float* aux, const float* U, float* dz, float* dzr, float* dh0, void* ws,
                size_t ws_bytes, int B, int T, int u, int act, int ract, int reset_after, int reverse, int dy_seq, void* stream);
+
+/* ---- a PAIR of GRU directions in one launch (csrc/gru.hip; keras layers.Bidirectional): gn_lstm_pair_fwd / _bwd's contract on the
+ * GRU kernels.  blockIdx.y is the direction; host tables of two device pointers; direction 0 walks with reverse0 and writes step s at position
+ * s, direction 1 walks with !reverse0 and writes it at position T-1-s; h / dy through `ld` >= u (two (B, T, u) buffers, or one (B, T, 2u) buffer
+ * at columns 0 and u with ld = 2u); seq / dy_seq == 0: a (B, ld) row buffer for the last processed step.  Each direction is bit for bit what
+ * gn_gru_fwd / gn_gru_bwd gives on the same operands; no initial state.  rbias and dzr (tables and entries) are required exactly under
+ * reset_after; gates, hprev and aux may be NULL without `training`.  The stored tensors, dz and dzr are per direction, contiguous, at the input
+ * time index.
+ * ws: TWICE gn_gru_fwd_workspace(u) / gn_gru_bwd_workspace(u) bytes, direction 0 first.
+ * GN_EINVAL, nothing launched: a NULL table or entry, ld < u, T < 1, u < 1 or u > 512, B < 0, an unknown activation code, reset_after not 0 or 1;
+ * GN_EWORKSPACE: ws too small.  B == 0 is GN_OK without a launch. */
+int gn_gru_pair_fwd(const float* const* zx, const float* const* U, const float* const* bias, const float* const* rbias, float* const* h, float* const* gates,
+                    float* const* hprev, float* const* aux, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
+                    int reverse0, int seq, int training, void* stream);
+int gn_gru_pair_bwd(const float* const* dy, const float* const* gates, const float* const* hprev, const float* const* aux, const float* const* U,
+                    float* const* dz, float* const* dzr, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
+                    int reverse0, int dy_seq, void* stream);
 
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
