@@ -5,6 +5,7 @@
     from gennet_amd.keras.layers.core import Activation, Flatten
     from gennet_amd.keras.layers.normalization import BatchNormalization
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
+    from gennet_amd.keras.layers.convolutional import SeparableConv1D  # also gennet_amd.keras.layers.SeparableConv1D
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU, Softmax
     from gennet_amd.keras.activations import softmax, relu, tanh, sigmoid, linear            # names for activation=
     from gennet_amd.keras import regularizers                          # l1, l2, l1_l2, L1L2, get, serialize, deserialize
@@ -62,7 +63,7 @@ def _pick(mod, *names):
 
 _core = _pick(_layers, 'Activation', 'ActivityRegularization', 'Dense', 'Dropout', 'Flatten', 'Reshape')
 _norm = _pick(_layers, 'BatchNormalization')
-_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'UpSampling1D', 'MaxPooling2D'),
+_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'SeparableConv1D', 'UpSampling1D', 'MaxPooling2D'),
              **_unused('37-38', 'UpSampling2D'))
 _conv.update((n, _pooling_placeholder(n, '37-38')) for n in ('AveragePooling1D', 'MaxPooling1D'))
 _pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'AveragePooling2D', 'GlobalAveragePooling1D', 'GlobalAveragePooling2D',

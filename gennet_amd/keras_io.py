@@ -242,6 +242,13 @@ def layer_config(layer):
             cfg.update(unit_forget_bias=layer.unit_forget_bias)
         else:
             cfg.update(reset_after=layer.reset_after)
+    elif isinstance(layer, L.SeparableConv1D):   # keras 2.2.4 layers/convolutional.py: _SeparableConv.get_config, rank and the kernel_* keys popped
+        cfg.update(filters=layer.filters, kernel_size=[layer.k], strides=[layer.stride], padding=layer.padding, data_format='channels_last',
+                   dilation_rate=[layer.dilation], activation=_ACT_OF_SPEC[layer.activation[0]], use_bias=True, bias_initializer=_ZEROS,
+                   bias_regularizer=_reg(layer.bias_regularizer), activity_regularizer=_reg(layer.activity_regularizer), bias_constraint=None,
+                   depth_multiplier=layer.depth_multiplier, depthwise_initializer=_GLOROT, pointwise_initializer=_GLOROT,
+                   depthwise_regularizer=_reg(layer.depthwise_regularizer), pointwise_regularizer=_reg(layer.pointwise_regularizer),
+                   depthwise_constraint=None, pointwise_constraint=None)
     elif isinstance(layer, L.Bidirectional):     # keras 2.2.4 layers/wrappers.py: Wrapper.get_config's 'layer' entry and merge_mode
         cfg.update(layer={'class_name': layer.layer.__class__.__name__, 'config': layer_config(layer.layer)}, merge_mode=layer.merge_mode)
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
@@ -371,6 +378,11 @@ def _layer_from_config(class_name, cfg, custom_objects):
                 'bias_constraint', 'dropout', 'recurrent_dropout', 'implementation', 'return_sequences', 'return_state', 'go_backwards', 'stateful',
                 'unroll')
         return getattr(L, class_name)(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
+    if class_name == 'SeparableConv1D':          # the layer itself refuses what it does not run, naming the key
+        keys = ('strides', 'padding', 'data_format', 'dilation_rate', 'depth_multiplier', 'activation', 'use_bias', 'depthwise_initializer',
+                'pointwise_initializer', 'bias_initializer', 'depthwise_regularizer', 'pointwise_regularizer', 'bias_regularizer',
+                'activity_regularizer', 'depthwise_constraint', 'pointwise_constraint', 'bias_constraint')
+        return L.SeparableConv1D(cfg['filters'], cfg['kernel_size'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
     if class_name == 'Bidirectional':            # the inner layer through the LSTM / GRU path above, with its own name and go_backwards
         inner = cfg['layer']
         if inner['class_name'] not in ('LSTM', 'GRU'):

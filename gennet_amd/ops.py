@@ -743,6 +743,65 @@ def gru_pair_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activati
     return dz, dzr
 
 
+# ---------------------------------------------------------------------------------------------- depthwise conv (csrc/depthwise.hip)
+def _dw_shape(what, t, w, channels):
+    """(k, C, dm) of a depthwise kernel w beside a float32 (B, rows, `channels` of them) tensor t"""
+    if t.dim() != 3 or w.dim() != 3 or t.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError('%s: float32 (B, rows, channels) beside a depthwise kernel (k, C, dm) is expected, got %r %s and %r %s'
+                         % (what, tuple(t.shape), t.dtype, tuple(w.shape), w.dtype))
+    k, C, dm = (int(v) for v in w.shape)
+    if int(t.shape[2]) != (C * dm if channels == 'out' else C):
+        raise ValueError('%s: %d channels beside a depthwise kernel %r (%s)' % (what, t.shape[2], (k, C, dm), 'C * dm' if channels == 'out' else 'C'))
+    return k, C, dm
+
+
+def dwconv1d_fwd(x, w, stride=1, padding='valid', dilation=1):
+    """y (B, Lout, C dm) of x (B, L, C) under the depthwise kernel w (k, C, dm), output channel c dm + m; geometry: conv_geometry (TF's 'same')."""
+    _chk(x, w)
+    k, C, dm = _dw_shape('dwconv1d_fwd', x, w, 'in')
+    B, L = int(x.shape[0]), int(x.shape[1])
+    Lout, pl = conv_geometry(L, k, stride, padding, dilation)
+    if Lout < 1:
+        raise ValueError('dwconv1d_fwd: %d taps (dilation %d, padding %r) on %d rows: the output would have %d rows' % (k, dilation, padding, L, Lout))
+    y = torch.empty((B, Lout, C * dm), dtype=torch.float32, device=x.device)
+    _lib.call('gn_dwconv1d_fwd', _p(x), _p(w), _p(y), B, L, C, k, dm, int(stride), int(dilation), pl, Lout, _stream())
+    return y
+
+
+def dwconv1d_dgrad(dy, w, L, stride=1, padding='valid', dilation=1):
+    """dx (B, L, C) from dy (B, Lout, C dm): every element gathers its (tap, m) pairs, no atomics."""
+    _chk(dy, w)
+    k, C, dm = _dw_shape('dwconv1d_dgrad', dy, w, 'out')
+    B = int(dy.shape[0])
+    Lout, pl = conv_geometry(int(L), k, stride, padding, dilation)
+    if int(dy.shape[1]) != Lout:
+        raise ValueError('dwconv1d_dgrad: dy has %d rows, the conv of %d rows has %d' % (dy.shape[1], L, Lout))
+    dx = torch.empty((B, int(L), C), dtype=torch.float32, device=dy.device)
+    _lib.call('gn_dwconv1d_dgrad', _p(dy), _p(w), _p(dx), B, int(L), C, k, dm, int(stride), int(dilation), pl, Lout, _stream())
+    return dx
+
+
+def dwconv1d_wgrad(x, dy, k, stride=1, padding='valid', dilation=1, dw=None):
+    """dw (k, C, dm) from x (B, L, C) and dy (B, Lout, C dm): per-block partial sums in ops.workspace, summed in a fixed order; written into `dw`
+    where given."""
+    _chk(x, dy, dw)
+    if x.dim() != 3 or dy.dim() != 3 or x.dtype != torch.float32 or dy.dtype != torch.float32 or x.shape[0] != dy.shape[0] or dy.shape[2] % x.shape[2]:
+        raise ValueError('dwconv1d_wgrad: float32 x (B, L, C) beside dy (B, Lout, C dm) is expected, got %r %s and %r %s'
+                         % (tuple(x.shape), x.dtype, tuple(dy.shape), dy.dtype))
+    B, L, C = (int(v) for v in x.shape)
+    k, dm = int(k), int(dy.shape[2]) // C
+    Lout, pl = conv_geometry(L, k, stride, padding, dilation)
+    if int(dy.shape[1]) != Lout:
+        raise ValueError('dwconv1d_wgrad: dy has %d rows, the conv of %d rows has %d' % (dy.shape[1], L, Lout))
+    if dw is None:
+        dw = torch.empty((k, C, dm), dtype=torch.float32, device=x.device)
+    elif dw.numel() != k * C * dm or dw.dtype != torch.float32:
+        raise ValueError('dwconv1d_wgrad: dw %r %s is no float32 (k, C, dm) = %r' % (tuple(dw.shape), dw.dtype, (k, C, dm)))
+    ws = workspace(_lib.size('gn_dwconv1d_wgrad_workspace', B, Lout, C, k, dm), x.device)
+    _lib.call('gn_dwconv1d_wgrad', _p(x), _p(dy), _p(dw), _p(ws), ws.numel(), B, L, C, k, dm, int(stride), int(dilation), pl, Lout, _stream())
+    return dw
+
+
 def dropout_mask(shape, rate, seed, offset, device):
     m = torch.empty(shape, dtype=torch.uint8, device=device)
     _lib.call('gn_dropout_mask', _p(m), m.numel(), float(rate), int(seed), int(offset), _stream())

@@ -508,6 +508,28 @@ int gn_gru_pair_bwd(const float* const* dy, const float* const* gates, const flo
                     float* const* dz, float* const* dzr, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
                     int reverse0, int dy_seq, void* stream);
 
+/* ---- depthwise 1-D convolution (csrc/depthwise.hip; the depthwise half of keras layers.SeparableConv1D).  Channels-last fp32:
+ * x (B, L, C), w (k, C, dm) = keras' depthwise_kernel, y / dy (B, Lout, C dm) with output channel c dm + m (tf.nn.depthwise_conv2d's order):
+ *   y[b, l, c dm + m] = sum_t x[b, l stride - pad_left + t dilation, c] * w[t, c, m]          (x outside [0, L) is 0)
+ *   dx[b, i, c]       = sum over the (t, m) with (i + pad_left - t dilation) % stride == 0 and that quotient in [0, Lout) of dy * w   (gather form)
+ *   dw[t, c, m]       = sum_{b, l} x[b, l stride - pad_left + t dilation, c] * dy[b, l, c dm + m]
+ * Three streaming passes, a thread per output, no atomics; C dm % 4 == 0 (dgrad: C % 4 == 0) on 16-byte aligned pointers moves 16 bytes a lane,
+ * anything else runs the scalar form of the same kernels.  Any C, k, dm, stride, dilation >= 1, pad_left >= 0, L, Lout >= 1 (rows outside the
+ * input are padding whatever Lout is), stride > 1 together with dilation > 1 included.  Every y is one fp32 fmaf chain from +0 over t, every dx
+ * one over (t, m) with t outer, both skipping the padding: a sample's y and dx do not depend on B, on the block or on the launch.
+ * gn_dwconv1d_wgrad: a block sums its own rows (a thread's fp32 fmaf chain over its rows in ascending order, the row lanes added in fp64 in lane
+ *   order) into ws, and the fixed-order fp64 pass behind gn_bias_grad sums the parts: bit-identical from run to run.
+ *   ws: gn_dwconv1d_wgrad_workspace(B, Lout, C, k, dm) bytes, 8-byte aligned (host only; 0 for a shape out of range or B == 0).
+ * GN_EINVAL, nothing launched: a NULL pointer, B < 0, any of L, C, k, dm, stride, dilation, Lout < 1, pad_left < 0, k * C * dm >= 2^31,
+ * B * L * C or B * Lout * C * dm >= 2^62, a workspace that is not 8-byte aligned; GN_EWORKSPACE: ws too small.  B == 0 is GN_OK without a launch. */
+size_t gn_dwconv1d_wgrad_workspace(int B, int Lout, int C, int k, int dm);
+int gn_dwconv1d_fwd(const float* x, const float* w, float* y, int B, int L, int C, int k, int dm, int stride, int dilation, int pad_left, int Lout,
+                    void* stream);
+int gn_dwconv1d_dgrad(const float* dy, const float* w, float* dx, int B, int L, int C, int k, int dm, int stride, int dilation, int pad_left, int Lout,
+                      void* stream);
+int gn_dwconv1d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int B, int L, int C, int k, int dm, int stride, int dilation,
+                      int pad_left, int Lout, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
