@@ -12,8 +12,8 @@
     from gennet_amd.keras.layers.noise import GaussianNoise, GaussianDropout, AlphaDropout
     from gennet_amd.keras.layers.pooling import MaxPooling1D, AveragePooling1D, GlobalAveragePooling1D, ...   # all eight pooling layers
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, Dot, add, dot, ...                   # all eight merge layers and functions
-    from gennet_amd.keras.layers.recurrent import LSTM, GRU            # also gennet_amd.keras.layers.LSTM, .GRU
-    from gennet_amd.keras.layers.wrappers import Bidirectional         # also gennet_amd.keras.layers.Bidirectional: over LSTM or GRU
+    from gennet_amd.keras.layers.recurrent import LSTM, GRU, SimpleRNN # also gennet_amd.keras.layers.LSTM, .GRU, .SimpleRNN
+    from gennet_amd.keras.layers.wrappers import Bidirectional         # also gennet_amd.keras.layers.Bidirectional: over LSTM, GRU or SimpleRNN
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -72,7 +72,7 @@ _act = dict(_pick(_layers, 'LeakyReLU', 'PReLU', 'ReLU', 'Softmax'), **_unused('
 _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate', 'Dot',
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
-_recurrent = _pick(_layers, 'LSTM', 'GRU')
+_recurrent = _pick(_layers, 'LSTM', 'GRU', 'SimpleRNN')
 _wrappers = _pick(_layers, 'Bidirectional')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')

@@ -231,16 +231,18 @@ def layer_config(layer):
         cfg.update(axis=layer.axis)
     elif isinstance(layer, L.Dot):               # axes as keras writes it: the int, or the pair as a list
         cfg.update(axes=layer.axes if isinstance(layer.axes, int) else list(layer.axes), normalize=layer.normalize)
-    elif isinstance(layer, (L.LSTM, L.GRU)):     # the keys of keras 2.2.4 layers/recurrent.py LSTM.get_config / GRU.get_config
+    elif isinstance(layer, (L.LSTM, L.GRU, L.SimpleRNN)):    # the keys of keras 2.2.4 layers/recurrent.py LSTM / GRU / SimpleRNN.get_config
         cfg.update(return_sequences=layer.return_sequences, return_state=False, go_backwards=layer.go_backwards, stateful=False, unroll=layer.unroll,
-                   units=layer.units, activation=layer.activation, recurrent_activation=layer.recurrent_activation, use_bias=True,
+                   units=layer.units, activation=layer.activation, use_bias=True,
                    kernel_initializer=_GLOROT, recurrent_initializer=_ORTHOGONAL, bias_initializer=_ZEROS,
                    kernel_regularizer=_reg(layer.kernel_regularizer), recurrent_regularizer=_reg(layer.recurrent_regularizer),
                    bias_regularizer=_reg(layer.bias_regularizer), activity_regularizer=_reg(layer.activity_regularizer), kernel_constraint=None,
-                   recurrent_constraint=None, bias_constraint=None, dropout=0.0, recurrent_dropout=0.0, implementation=layer.implementation)
+                   recurrent_constraint=None, bias_constraint=None, dropout=0.0, recurrent_dropout=0.0)
+        if not isinstance(layer, L.SimpleRNN):   # SimpleRNN writes neither
+            cfg.update(recurrent_activation=layer.recurrent_activation, implementation=layer.implementation)
         if isinstance(layer, L.LSTM):
             cfg.update(unit_forget_bias=layer.unit_forget_bias)
-        else:
+        elif isinstance(layer, L.GRU):
             cfg.update(reset_after=layer.reset_after)
     elif isinstance(layer, L.SeparableConv1D):   # keras 2.2.4 layers/convolutional.py: _SeparableConv.get_config, rank and the kernel_* keys popped
         cfg.update(filters=layer.filters, kernel_size=[layer.k], strides=[layer.stride], padding=layer.padding, data_format='channels_last',
@@ -378,15 +380,20 @@ def _layer_from_config(class_name, cfg, custom_objects):
                 'bias_constraint', 'dropout', 'recurrent_dropout', 'implementation', 'return_sequences', 'return_state', 'go_backwards', 'stateful',
                 'unroll')
         return getattr(L, class_name)(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
+    if class_name == 'SimpleRNN':                # as LSTM / GRU, without recurrent_activation and implementation
+        keys = ('activation', 'use_bias', 'kernel_initializer', 'recurrent_initializer', 'bias_initializer', 'kernel_regularizer',
+                'recurrent_regularizer', 'bias_regularizer', 'activity_regularizer', 'kernel_constraint', 'recurrent_constraint', 'bias_constraint',
+                'dropout', 'recurrent_dropout', 'return_sequences', 'return_state', 'go_backwards', 'stateful', 'unroll')
+        return L.SimpleRNN(cfg['units'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
     if class_name == 'SeparableConv1D':          # the layer itself refuses what it does not run, naming the key
         keys = ('strides', 'padding', 'data_format', 'dilation_rate', 'depth_multiplier', 'activation', 'use_bias', 'depthwise_initializer',
                 'pointwise_initializer', 'bias_initializer', 'depthwise_regularizer', 'pointwise_regularizer', 'bias_regularizer',
                 'activity_regularizer', 'depthwise_constraint', 'pointwise_constraint', 'bias_constraint')
         return L.SeparableConv1D(cfg['filters'], cfg['kernel_size'], **dict((k, cfg[k]) for k in keys if k in cfg), **kw)
-    if class_name == 'Bidirectional':            # the inner layer through the LSTM / GRU path above, with its own name and go_backwards
+    if class_name == 'Bidirectional':            # the inner layer through the LSTM / GRU / SimpleRNN paths above, with its own name and go_backwards
         inner = cfg['layer']
-        if inner['class_name'] not in ('LSTM', 'GRU'):
-            raise ValueError('Bidirectional wraps an LSTM or a GRU, not %s' % inner['class_name'])
+        if inner['class_name'] not in ('LSTM', 'GRU', 'SimpleRNN'):
+            raise ValueError('Bidirectional wraps an LSTM or a GRU, or a SimpleRNN, not %s' % inner['class_name'])
         return L.Bidirectional(_layer_from_config(inner['class_name'], inner['config'], None), merge_mode=cfg.get('merge_mode', 'concat'), **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 

@@ -1505,9 +1505,9 @@ def concatenate(inputs, axis=-1, **kw):
 # keras.layers.Dot / dot live in gennet_amd/dot.py and are part of this name space
 from .dot import Dot, dot  # noqa: E402,F401
 
-# keras.layers.LSTM, keras.layers.GRU and keras.layers.Bidirectional live in gennet_amd/recurrent.py and are part of this
-# name space
-from .recurrent import GRU, LSTM, Bidirectional  # noqa: E402,F401
+# keras.layers.LSTM, keras.layers.GRU, keras.layers.SimpleRNN and keras.layers.Bidirectional live in gennet_amd/recurrent.py (DESIGN 8o - 8q,
+# 8s) and are part of this name space
+from .recurrent import GRU, LSTM, Bidirectional, SimpleRNN  # noqa: E402,F401
 
 # keras.layers.SeparableConv1D lives in gennet_amd/separable.py and is part of this name space
 from .separable import SeparableConv1D  # noqa: E402,F401

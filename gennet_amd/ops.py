@@ -629,6 +629,45 @@ def gru_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activation='h
     return dz, dzr, dh0
 
 
+# ---------------------------------------------------------------------------------------------- SimpleRNN recurrence (csrc/rnn.hip)
+def _rnn_shape(what, zx, U):
+    if zx.dim() != 3 or U.dim() != 2 or U.shape[1] != U.shape[0] or zx.shape[2] != U.shape[1] or zx.dtype != torch.float32 or U.dtype != torch.float32:
+        raise ValueError('%s: float32 (B, T, u) beside a recurrent kernel (u, u) is expected, got %r and %r' % (what, tuple(zx.shape), tuple(U.shape)))
+    return int(zx.shape[0]), int(zx.shape[1]), int(U.shape[0])
+
+
+def rnn_fwd(zx, U, bias, h0=None, activation='tanh', reverse=False, training=False):
+    """The SimpleRNN recurrence h_t = act((zx_t + b) + h_{t-1} . U) over zx (B, T, u) = X . W: -> (h, hs, hprev).  h (B, T, u) is in processing
+    order (under `reverse` step s reads zx[:, T-1-s]); in the training phase hs (B, T, u) = h_t and hprev (B, T, u), the h that entered each
+    step, are stored at the input time index for rnn_bwd and the weight gradients, else they are None.  h0 (B, u): None is zeros."""
+    _chk(zx, U, bias, h0)
+    B, T, u = _rnn_shape('rnn_fwd', zx, U)
+    assert bias.numel() == u and (h0 is None or tuple(h0.shape) == (B, u))
+    h = torch.empty((B, T, u), dtype=torch.float32, device=zx.device)
+    hs = hprev = None
+    if training:
+        hs, hprev = torch.empty_like(h), torch.empty_like(h)
+    ws = workspace(_lib.size('gn_rnn_fwd_workspace', u), zx.device)
+    _lib.call('gn_rnn_fwd', _p(zx), _p(U), _p(bias), _p(h0), _p(h), _p(hs), _p(hprev), _p(ws), ws.numel(), B, T, u, LSTM_ACT[activation],
+              int(bool(reverse)), int(bool(training)), _stream())
+    return h, hs, hprev
+
+
+def rnn_bwd(dy, hs, U, activation='tanh', reverse=False, want_state_grad=False):
+    """Backward through time from the h_t rnn_fwd stored: dy (B, T, u) in processing order, or (B, u) for the last step only.
+    -> (dz (B, T, u) at the input time index, dh0 (B, u) only under want_state_grad, else None)."""
+    _chk(dy, hs, U)
+    B, T, u = _rnn_shape('rnn_bwd', hs, U)
+    if tuple(dy.shape) not in ((B, T, u), (B, u)):
+        raise ValueError('rnn_bwd: dy %r beside hs %r' % (tuple(dy.shape), tuple(hs.shape)))
+    dz = torch.empty_like(hs)
+    dh0 = torch.empty((B, u), dtype=torch.float32, device=dy.device) if want_state_grad else None
+    ws = workspace(_lib.size('gn_rnn_bwd_workspace', u), dy.device)
+    _lib.call('gn_rnn_bwd', _p(dy), _p(hs), _p(U), _p(dz), _p(dh0), _p(ws), ws.numel(), B, T, u, LSTM_ACT[activation], int(bool(reverse)),
+              int(dy.dim() == 3), _stream())
+    return dz, dh0
+
+
 # ------------------------------------------------------------------ a pair of directions in one launch (keras Bidirectional; DESIGN 8q)
 def _pair(what, ts):
     ts = list(ts)
@@ -741,6 +780,38 @@ def gru_pair_bwd(dy, gates, hprev, aux, U, activation='tanh', recurrent_activati
               _ptr_table(dzr or [None, None]), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation], LSTM_ACT[recurrent_activation],
               int(bool(reset_after)), int(bool(reverse0)), int(dy_seq), _stream())
     return dz, dzr
+
+
+def rnn_pair_fwd(zx, U, bias, activation='tanh', reverse0=False, seq=True, concat=True, training=False):
+    """lstm_pair_fwd for the SimpleRNN: -> (y, h, hs, hprev), hs and hprev lists of two as rnn_fwd stores them, or None outside the training phase."""
+    zx, U, bias = _pair('rnn_pair_fwd', zx), _pair('rnn_pair_fwd', U), _pair('rnn_pair_fwd', bias)
+    _chk(*(zx + U + bias))
+    B, T, u = _rnn_shape('rnn_pair_fwd', zx[0], U[0])
+    assert (B, T, u) == _rnn_shape('rnn_pair_fwd', zx[1], U[1]) and all(b.numel() == u for b in bias)
+    dev = zx[0].device
+    h, ld, y = _pair_out(B, T, u, concat, seq, dev)
+    hs = hprev = None
+    if training:
+        hs, hprev = ([torch.empty((B, T, u), dtype=torch.float32, device=dev) for _ in range(2)] for _ in range(2))
+    ws = workspace(2 * _lib.size('gn_rnn_fwd_workspace', u), dev)
+    _lib.call('gn_rnn_pair_fwd', _ptr_table(zx), _ptr_table(U), _ptr_table(bias), _ptr_table(h), _ptr_table(hs or [None, None]),
+              _ptr_table(hprev or [None, None]), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation], int(bool(reverse0)), int(bool(seq)),
+              int(bool(training)), _stream())
+    return y, h, hs, hprev
+
+
+def rnn_pair_bwd(dy, hs, U, activation='tanh', reverse0=False, concat=True):
+    """lstm_pair_bwd for the SimpleRNN: -> [dz_0, dz_1], each (B, T, u) at the input time index, as rnn_bwd forms them."""
+    hs, U = _pair('rnn_pair_bwd', hs), _pair('rnn_pair_bwd', U)
+    _chk(*(hs + U))
+    B, T, u = _rnn_shape('rnn_pair_bwd', hs[0], U[0])
+    assert (B, T, u) == _rnn_shape('rnn_pair_bwd', hs[1], U[1])
+    dys, ld, dy_seq = _pair_dy('rnn_pair_bwd', dy, B, T, u, concat)
+    dz = [torch.empty_like(t) for t in hs]
+    ws = workspace(2 * _lib.size('gn_rnn_bwd_workspace', u), dz[0].device)
+    _lib.call('gn_rnn_pair_bwd', _ptr_table(dys), _ptr_table(hs), _ptr_table(U), _ptr_table(dz), _p(ws), ws.numel(), B, T, u, ld, LSTM_ACT[activation],
+              int(bool(reverse0)), int(dy_seq), _stream())
+    return dz
 
 
 # ---------------------------------------------------------------------------------------------- depthwise conv (csrc/depthwise.hip, DESIGN 8r)

@@ -1,5 +1,6 @@
-"""keras.layers.LSTM and keras.layers.GRU (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrences of csrc/lstm.hip and
-csrc/gru.hip; DESIGN 8o, 8p.  keras.layers.Bidirectional (layers/wrappers.py) over either: both directions in one launch; DESIGN 8q.
+"""keras.layers.LSTM, keras.layers.GRU and keras.layers.SimpleRNN (keras 2.2.4 layers/recurrent.py) on the persistent fp32 matrix-core recurrences
+of csrc/lstm.hip, csrc/gru.hip and csrc/rnn.hip; DESIGN 8o, 8p, 8s.  keras.layers.Bidirectional (layers/wrappers.py) over any of them: both
+directions in one launch; DESIGN 8q.
 
 The classes are part of the gennet_amd.layers name space (gennet_amd.layers.LSTM is this LSTM), as every layer is."""
 import numpy as np
@@ -9,6 +10,7 @@ from .engine import Layer
 
 _ACTIVATIONS = ('tanh', 'sigmoid', 'relu', 'linear')
 _RECURRENT_ACTIVATIONS = ('hard_sigmoid', 'sigmoid')
+_ABSENT = object()                  # what SimpleRNN hands _init_recurrent for the keys its constructor does not have
 
 
 def _name_of(v):
@@ -60,8 +62,9 @@ def rows_product(a, dz, out):
 def _init_recurrent(layer, what, kw, units, activation, recurrent_activation, use_bias, kernel_initializer, recurrent_initializer, bias_initializer,
                     kernel_regularizer, recurrent_regularizer, bias_regularizer, activity_regularizer, return_sequences, go_backwards,
                     implementation, unroll):
-    """What LSTM and GRU share of their constructors: the refusals, each naming its key (`what` is the class name), Layer.__init__ over the rest
-    of kw, and the attributes both configs write."""
+    """What LSTM, GRU and SimpleRNN share of their constructors: the refusals, each naming its key (`what` is the class name), Layer.__init__ over
+    the rest of kw, and the attributes the configs write.  SimpleRNN has no recurrent_activation and no implementation: it hands _ABSENT for
+    both, and neither is checked or set."""
     for key in ('dropout', 'recurrent_dropout'):
         if float(kw.pop(key, 0.0) or 0.0) != 0.0:
             raise NotImplementedError('%s(%s=...): dropout inside the cell is not implemented; only 0 runs' % (what, key))
@@ -73,11 +76,11 @@ def _init_recurrent(layer, what, kw, units, activation, recurrent_activation, us
             raise NotImplementedError('%s(%s=...): weight constraints are not implemented' % (what, key))
     if not use_bias:
         raise NotImplementedError('%s(use_bias=False)' % what)
-    act, ract = _name_of(activation), _name_of(recurrent_activation)
+    act, ract = _name_of(activation), recurrent_activation if recurrent_activation is _ABSENT else _name_of(recurrent_activation)
     act = 'linear' if act is None else act
     if act not in _ACTIVATIONS:
         raise NotImplementedError('%s(activation=%r): one of %s' % (what, activation, ', '.join(_ACTIVATIONS)))
-    if ract not in _RECURRENT_ACTIVATIONS:
+    if ract is not _ABSENT and ract not in _RECURRENT_ACTIVATIONS:
         raise NotImplementedError('%s(recurrent_activation=%r): one of %s' % (what, recurrent_activation, ', '.join(_RECURRENT_ACTIVATIONS)))
     if not _initializer_is(kernel_initializer, 'glorot_uniform', ('GlorotUniform', 'VarianceScaling'), mode='fan_avg', distribution='uniform'):
         raise NotImplementedError('%s(kernel_initializer=%r): only glorot_uniform' % (what, kernel_initializer))
@@ -85,22 +88,26 @@ def _init_recurrent(layer, what, kw, units, activation, recurrent_activation, us
         raise NotImplementedError('%s(recurrent_initializer=%r): only orthogonal' % (what, recurrent_initializer))
     if not _initializer_is(bias_initializer, 'zeros', ('Zeros',)):
         raise NotImplementedError('%s(bias_initializer=%r): only zeros' % (what, bias_initializer))
-    if implementation not in (1, 2):
+    if implementation is not _ABSENT and implementation not in (1, 2):
         raise ValueError('%s(implementation=%r): 1 or 2' % (what, implementation))
     Layer.__init__(layer, **kw)
     layer.units = int(units)
     if layer.units < 1:
         raise ValueError('%s(units=%r): at least 1' % (what, units))
-    layer.activation, layer.recurrent_activation = act, ract
+    layer.activation = act
+    if ract is not _ABSENT:
+        layer.recurrent_activation = ract
     layer.kernel_regularizer, layer.recurrent_regularizer = regularizers.get(kernel_regularizer), regularizers.get(recurrent_regularizer)
     layer.bias_regularizer, layer.activity_regularizer = regularizers.get(bias_regularizer), regularizers.get(activity_regularizer)
     layer.return_sequences, layer.go_backwards = bool(return_sequences), bool(go_backwards)
-    layer.implementation, layer.unroll = int(implementation), bool(unroll)
+    layer.unroll = bool(unroll)
+    if implementation is not _ABSENT:
+        layer.implementation = int(implementation)
 
 
 def _add_triple(owner, cell, prefix, Cin):
-    """kernel (Cin, G u), recurrent_kernel (u, G u) and bias of `cell` (an LSTM or a GRU) as Params of `owner` under `prefix`, drawn in keras'
-    order from the generator glorot_uniform draws from, each with the cell's regularizer"""
+    """kernel (Cin, G u), recurrent_kernel (u, G u) and bias of `cell` (an LSTM, a GRU or a SimpleRNN) as Params of `owner` under `prefix`, drawn in
+    keras' order from the generator glorot_uniform draws from, each with the cell's regularizer"""
     u, G = cell.units, cell.n_gates
     return (owner.add_weight(prefix + 'kernel', engine.glorot_uniform((Cin, G * u)), regularizer=cell.kernel_regularizer),
             owner.add_weight(prefix + 'recurrent_kernel', orthogonal_blocks(u, G), regularizer=cell.recurrent_regularizer),
@@ -269,16 +276,84 @@ class LSTM(Layer):
         ops.bias_grad(dz2, bias.grad)
 
 
+class SimpleRNN(Layer):
+    """keras.layers.SimpleRNN(units): (B, T, Cin) -> (B, units), or (B, T, units) with return_sequences.  SimpleRNNCell of keras 2.2.4 with
+    kernel (Cin, u), recurrent_kernel (u, u) and bias (u):
+        h_t = act(x_t . W + b + h_{t-1} . U)
+    with act one of tanh, sigmoid, relu, linear; h_0 = 0.  There is no recurrent activation, no implementation and no reset_after; go_backwards
+    and unroll as in LSTM.
+    Forward: zx = X . W as one gn_bmm over B T rows, then gn_rnn_fwd, one launch that walks the T steps with h on chip.
+    Backward: gn_rnn_bwd walks the steps down and writes dz (B, T, u): dW = X^T dz, dU = hprev^T dz (rows_product), db = sum dz, dX = dz W^T.
+    The tape keeps x, hprev and the stored h_t (a tensor of its own, not the layer's output), in the training phase only.  The planner fuses
+    nothing onto the layer, and dy is not written."""
+
+    def __init__(self, units, activation='tanh', use_bias=True, kernel_initializer='glorot_uniform', recurrent_initializer='orthogonal',
+                 bias_initializer='zeros', kernel_regularizer=None, recurrent_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 return_sequences=False, go_backwards=False, unroll=False, **kw):
+        for key in ('recurrent_activation', 'implementation', 'reset_after', 'unit_forget_bias'):
+            if key in kw:
+                raise TypeError('SimpleRNN(%s=...): keras.layers.SimpleRNN has no such argument' % key)
+        _init_recurrent(self, 'SimpleRNN', kw, units, activation, _ABSENT, use_bias, kernel_initializer, recurrent_initializer, bias_initializer,
+                        kernel_regularizer, recurrent_regularizer, bias_regularizer, activity_regularizer, return_sequences, go_backwards,
+                        _ABSENT, unroll)
+
+    def build(self, input_shape):
+        if len(input_shape) != 2:
+            raise ValueError('%s (SimpleRNN) expects (batch, timesteps, features), got %r' % (self.name, (None,) + tuple(input_shape)))
+        Cin, u = int(input_shape[1]), self.units
+        if u > 512:
+            raise NotImplementedError('%s: SimpleRNN(units=%d): at most 512 units run (a block carries all units of its samples on chip)'
+                                      % (self.name, u))
+        self.kernel, self.recurrent_kernel, self.bias = _add_triple(self, self, '', Cin)
+
+    n_gates = 1
+
+    def initial_bias(self):
+        return np.zeros(self.units, np.float32)
+
+    def compute_output_shape(self, input_shape):
+        return (int(input_shape[0]), self.units) if self.return_sequences else (self.units,)
+
+    def forward(self, ctx, node, x):
+        x = x.contiguous()
+        B, T, Cin = x.shape
+        u = self.units
+        zx = ops.bmm(x.view(1, B * T, Cin), self.kernel.data.view(1, Cin, u)).view(B, T, u)
+        h, hs, hprev = ops.rnn_fwd(zx, self.recurrent_kernel.data, self.bias.data, None, self.activation, reverse=self.go_backwards,
+                                   training=ctx.training)
+        if ctx.training:
+            ctx.tape[node.index] = (x, hprev, hs)
+        return h if self.return_sequences else h[:, T - 1, :].contiguous()
+
+    def backward(self, ctx, node, dy, need_dx, need_dw):
+        x, hprev, hs = ctx.tape.pop(node.index)
+        B, T, _ = x.shape
+        u = self.units
+        dz, _ = ops.rnn_bwd(dy.contiguous().view((B, T, u) if self.return_sequences else (B, u)), hs, self.recurrent_kernel.data, self.activation,
+                            reverse=self.go_backwards)
+        if need_dw:
+            self.weight_grads(x, (hprev, hs, None), dz, None, self.kernel, self.recurrent_kernel, self.bias)
+        return _input_grad(dz, self.kernel, x.shape) if need_dx else None
+
+    def weight_grads(self, x, kept, dz, dzr, kernel, recurrent_kernel, bias):
+        """the gradients of one direction's three weights from what its recurrence stored (kept = hprev, hs, None) and its backward wrote"""
+        B, T, Cin = x.shape
+        dz2 = dz.view(B * T, self.units)
+        rows_product(x.view(B * T, Cin), dz2, kernel.grad)
+        rows_product(kept[0].view(B * T, self.units), dz2, recurrent_kernel.grad)
+        ops.bias_grad(dz2, bias.grad)
+
+
 _MERGE_PASS = {'sum': 'add', 'mul': 'mul', 'ave': 'avg'}          # merge_mode -> the mode of ops.merge_fwd
 
 
 class Bidirectional(Layer):
-    """keras.layers.Bidirectional(layer, merge_mode='concat') (keras 2.2.4 layers/wrappers.py) over an unbuilt LSTM or GRU of this module:
+    """keras.layers.Bidirectional(layer, merge_mode='concat') (keras 2.2.4 layers/wrappers.py) over an unbuilt LSTM, GRU or SimpleRNN of this module:
     (B, T, Cin) -> (B, [T,] 2u) for 'concat', (B, [T,] u) for 'sum', 'mul' and 'ave'.  The forward copy walks as the inner layer's go_backwards
     says, the backward copy the other way, and with return_sequences the backward copy's sequence is turned round (K.reverse along time)
     before the halves are merged.  Six weights in keras' order: <name>/forward_<inner>/{kernel, recurrent_kernel, bias}, then the same under
     backward_<inner>; each carries the inner layer's regularizer, and the forward triple is drawn first (what a lone inner layer draws).
-    Forward: zx_d = X . W_d, two gn_bmm; then ONE pair launch (ops.lstm_pair_fwd / gru_pair_fwd: the direction is the grid's second dimension)
+    Forward: zx_d = X . W_d, two gn_bmm; then ONE pair launch (ops.lstm_pair_fwd / gru_pair_fwd / rnn_pair_fwd: the direction is the grid's second dimension)
     that writes both halves in time-aligned order -- for 'concat' straight into the (B, [T,] 2u) output, so no reverse and no concatenate pass
     exists; for the other modes into two buffers that ops.merge_fwd joins.
     Backward: 'concat' and 'sum' hand dy to the pair launch as it is (read through a row stride), 'ave' one ops.scale by 1/2 shared by both
@@ -288,8 +363,8 @@ class Bidirectional(Layer):
     layer, and dy is not written."""
 
     def __init__(self, layer, merge_mode='concat', **kw):
-        if not isinstance(layer, (LSTM, GRU)):
-            raise ValueError('Please initialize `Bidirectional` layer with an unbuilt `LSTM` or `GRU` instance. You passed: %r' % (layer,))
+        if not isinstance(layer, (LSTM, GRU, SimpleRNN)):
+            raise ValueError('Please initialize `Bidirectional` layer with an unbuilt `LSTM`, `GRU` or `SimpleRNN` instance. You passed: %r' % (layer,))
         if layer.built:
             raise ValueError('Bidirectional(layer=%s): the inner layer is already built; the wrapper owns both copies of its weights' % layer.name)
         if merge_mode is None:
@@ -327,11 +402,16 @@ class Bidirectional(Layer):
         triples = (self.forward_weights, self.backward_weights)
         zx = [ops.bmm(x.view(1, B * T, Cin), W.data.view(1, Cin, G)).view(B, T, G) for W, _, _ in triples]
         U = [t[1].data for t in triples]
-        kw = dict(activation=inner.activation, recurrent_activation=inner.recurrent_activation, reverse0=inner.go_backwards,
-                  seq=inner.return_sequences, concat=self.merge_mode == 'concat', training=ctx.training)
-        if isinstance(inner, LSTM):
+        kw = dict(activation=inner.activation, reverse0=inner.go_backwards, seq=inner.return_sequences, concat=self.merge_mode == 'concat',
+                  training=ctx.training)
+        if isinstance(inner, SimpleRNN):
+            y, h, gates, hprev = ops.rnn_pair_fwd(zx, U, [t[2].data for t in triples], **kw)                      # gates: the stored h_t
+            last = [None, None]
+        elif isinstance(inner, LSTM):
+            kw['recurrent_activation'] = inner.recurrent_activation
             y, h, gates, last, hprev = ops.lstm_pair_fwd(zx, U, [t[2].data for t in triples], **kw)                 # last: c
         else:
+            kw['recurrent_activation'] = inner.recurrent_activation
             b2 = [t[2].data.view(-1, G) for t in triples]
             y, h, gates, hprev, last = ops.gru_pair_fwd(zx, U, [b[0] for b in b2], [b[1] for b in b2] if inner.reset_after else None,
                                                         reset_after=inner.reset_after, **kw)                      # last: aux
@@ -351,12 +431,13 @@ class Bidirectional(Layer):
             dy = [dy, dy]
         triples = (self.forward_weights, self.backward_weights)
         U = [t[1].data for t in triples]
-        kw = dict(activation=inner.activation, recurrent_activation=inner.recurrent_activation, reverse0=inner.go_backwards,
-                  concat=self.merge_mode == 'concat')
-        if isinstance(inner, LSTM):
-            dz, dzr = ops.lstm_pair_bwd(dy, gates, last, U, **kw), None
+        kw = dict(activation=inner.activation, reverse0=inner.go_backwards, concat=self.merge_mode == 'concat')
+        if isinstance(inner, SimpleRNN):
+            dz, dzr = ops.rnn_pair_bwd(dy, gates, U, **kw), None
+        elif isinstance(inner, LSTM):
+            dz, dzr = ops.lstm_pair_bwd(dy, gates, last, U, recurrent_activation=inner.recurrent_activation, **kw), None
         else:
-            dz, dzr = ops.gru_pair_bwd(dy, gates, hprev, last, U, reset_after=inner.reset_after, **kw)
+            dz, dzr = ops.gru_pair_bwd(dy, gates, hprev, last, U, recurrent_activation=inner.recurrent_activation, reset_after=inner.reset_after, **kw)
         if need_dw:
             for d, (W, Ud, b) in enumerate(triples):
                 inner.weight_grads(x, (hprev[d], gates[d], last[d]), dz[d], dzr[d] if dzr else None, W, Ud, b)

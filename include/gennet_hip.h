@@ -508,6 +508,43 @@ int gn_gru_pair_bwd(const float* const* dy, const float* const* gates, const flo
                     float* const* dz, float* const* dzr, void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int ract, int reset_after,
                     int reverse0, int dy_seq, void* stream);
 
+/* ---- SimpleRNN recurrence (csrc/rnn.hip; keras layers.SimpleRNN, SimpleRNNCell of keras 2.2.4).  One gate block of width u:
+ *   h_t = act((zx_t + b) + h_{t-1} . U)
+ * with enum gn_lstm_act's activation codes TANH, SIGMOID, RELU or LINEAR; there is no recurrent activation.  Ownership and numerics are the
+ * LSTM and GRU recurrences': one block carries 16 batch rows through all T steps, h stays on chip, the product runs on v_mfma_f32_16x16x4_f32,
+ * no block waits on another, no atomics.  The recurrent pre-activation is one fp32 fma chain over k from +0, then + (zx + b), and dh_{t-1} one
+ * chain over k, so a sample's results do not depend on B, on its tile or on the launch.  1 <= u <= 512; any B, T >= 1; 4-byte aligned pointers.
+ * gn_rnn_fwd: zx (B, T, u) = X . W, U (u, u), bias (u), h0 (B, u) or NULL (zeros).  Step s reads zx at the input time t = s, or T-1-s under
+ *   `reverse`, and writes h[:, s] (processing order).  With `training` it also stores at the INPUT time t: hs (B, T, u) = h_t, which the
+ *   backward's act' reads, and hprev (B, T, u), the h that entered the step (h0 at the first); without it nothing but h is written and hs and
+ *   hprev may be NULL.
+ * gn_rnn_bwd: dy (B, T, u) in processing order (dy_seq) or (B, u) for the last step only; hs as stored.  Walks the steps backwards,
+ *   dz_t = (dy_t + dh_t) act'(h_t), dh_{t-1} = dz_t . U^T, and writes dz (B, T, u) at the input time index (dW = X^T dz, dU = hprev^T dz,
+ *   dX = dz W^T, db = sum dz); dh0 (B, u) when not NULL.
+ * ws: gn_rnn_fwd_workspace(u) / gn_rnn_bwd_workspace(u) bytes (the zero-padded U / U^T the kernels read); 0 for a u out of range.
+ * GN_EINVAL, nothing launched: a NULL pointer, T < 1, u < 1 or u > 512, B < 0, an unknown or HARD_SIGMOID activation code; GN_EWORKSPACE: ws too
+ * small.  B == 0 is GN_OK without a launch. */
+size_t gn_rnn_fwd_workspace(int u);
+size_t gn_rnn_bwd_workspace(int u);
+int gn_rnn_fwd(const float* zx, const float* U, const float* bias, const float* h0, float* h, float* hs, float* hprev, void* ws, size_t ws_bytes, int B,
+               int T, int u, int act, int reverse, int training, void* stream);
+int gn_rnn_bwd(const float* dy, const float* hs, const float* U, float* dz, float* dh0, void* ws, size_t ws_bytes, int B, int T, int u, int act,
+               int reverse, int dy_seq, void* stream);
+
+/* ---- a PAIR of SimpleRNN directions in one launch (csrc/rnn.hip; keras layers.Bidirectional): gn_gru_pair_fwd / _bwd's contract on
+ * the SimpleRNN kernels.  blockIdx.y is the direction; host tables of two device pointers; direction 0 walks with reverse0 and writes step s at
+ * position s, direction 1 walks with !reverse0 and writes it at position T-1-s; h / dy through `ld` >= u (two (B, T, u) buffers, or one
+ * (B, T, 2u) buffer at columns 0 and u with ld = 2u); seq / dy_seq == 0: a (B, ld) row buffer for the last processed step.  Each direction is
+ * bit for bit what gn_rnn_fwd / gn_rnn_bwd gives on the same operands; no initial state.  hs and hprev (tables and entries) may be NULL without
+ * `training`.  The stored tensors and dz are per direction, contiguous, at the input time index.
+ * ws: TWICE gn_rnn_fwd_workspace(u) / gn_rnn_bwd_workspace(u) bytes, direction 0 first.
+ * GN_EINVAL, nothing launched: a NULL table or entry, ld < u, T < 1, u < 1 or u > 512, B < 0, an unknown or HARD_SIGMOID activation code;
+ * GN_EWORKSPACE: ws too small.  B == 0 is GN_OK without a launch. */
+int gn_rnn_pair_fwd(const float* const* zx, const float* const* U, const float* const* bias, float* const* h, float* const* hs, float* const* hprev,
+                    void* ws, size_t ws_bytes, int B, int T, int u, int ld, int act, int reverse0, int seq, int training, void* stream);
+int gn_rnn_pair_bwd(const float* const* dy, const float* const* hs, const float* const* U, float* const* dz, void* ws, size_t ws_bytes, int B, int T,
+                    int u, int ld, int act, int reverse0, int dy_seq, void* stream);
+
 /* ---- depthwise 1-D convolution (csrc/depthwise.hip; the depthwise half of keras layers.SeparableConv1D).  Channels-last fp32:
  * x (B, L, C), w (k, C, dm) = keras' depthwise_kernel, y / dy (B, Lout, C dm) with output channel c dm + m (tf.nn.depthwise_conv2d's order):
  *   y[b, l, c dm + m] = sum_t x[b, l stride - pad_left + t dilation, c] * w[t, c, m]          (x outside [0, L) is 0)
