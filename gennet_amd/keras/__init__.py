@@ -14,6 +14,9 @@
     from gennet_amd.keras.layers.merge import Add, Subtract, Concatenate, Dot, add, dot, ...                   # all eight merge layers and functions
     from gennet_amd.keras.layers.recurrent import LSTM, GRU, SimpleRNN # also gennet_amd.keras.layers.LSTM, .GRU, .SimpleRNN
     from gennet_amd.keras.layers.wrappers import Bidirectional         # also gennet_amd.keras.layers.Bidirectional: over LSTM, GRU or SimpleRNN
+    from gennet_amd.keras.layers.wrappers import TimeDistributed       # over Dense; also gennet_amd.keras.layers.TimeDistributed
+    from gennet_amd.keras.layers.core import RepeatVector, Permute     # also gennet_amd.keras.layers.RepeatVector, .Permute
+    from gennet_amd.keras.layers.convolutional import Cropping1D, ZeroPadding1D   # also gennet_amd.keras.layers.Cropping1D, .ZeroPadding1D
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -61,9 +64,9 @@ def _pick(mod, *names):
     return dict((n, getattr(mod, n)) for n in names)
 
 
-_core = _pick(_layers, 'Activation', 'ActivityRegularization', 'Dense', 'Dropout', 'Flatten', 'Reshape')
+_core = _pick(_layers, 'Activation', 'ActivityRegularization', 'Dense', 'Dropout', 'Flatten', 'Reshape', 'RepeatVector', 'Permute')
 _norm = _pick(_layers, 'BatchNormalization')
-_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'SeparableConv1D', 'UpSampling1D', 'MaxPooling2D'),
+_conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'SeparableConv1D', 'UpSampling1D', 'MaxPooling2D', 'Cropping1D', 'ZeroPadding1D'),
              **_unused('37-38', 'UpSampling2D'))
 _conv.update((n, _pooling_placeholder(n, '37-38')) for n in ('AveragePooling1D', 'MaxPooling1D'))
 _pooling = _pick(_layers, 'MaxPooling1D', 'MaxPooling2D', 'AveragePooling1D', 'AveragePooling2D', 'GlobalAveragePooling1D', 'GlobalAveragePooling2D',
@@ -73,7 +76,7 @@ _noise = _pick(_layers, 'GaussianNoise', 'GaussianDropout', 'AlphaDropout')
 _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Minimum', 'Concatenate', 'Dot',
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
 _recurrent = _pick(_layers, 'LSTM', 'GRU', 'SimpleRNN')
-_wrappers = _pick(_layers, 'Bidirectional')
+_wrappers = _pick(_layers, 'Bidirectional', 'TimeDistributed')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))

@@ -253,6 +253,16 @@ def layer_config(layer):
                    depthwise_constraint=None, pointwise_constraint=None)
     elif isinstance(layer, L.Bidirectional):     # keras 2.2.4 layers/wrappers.py: Wrapper.get_config's 'layer' entry and merge_mode
         cfg.update(layer={'class_name': layer.layer.__class__.__name__, 'config': layer_config(layer.layer)}, merge_mode=layer.merge_mode)
+    elif isinstance(layer, L.TimeDistributed):   # keras 2.2.4 layers/wrappers.py: Wrapper.get_config, the base config and the 'layer' entry
+        cfg.update(layer={'class_name': layer.layer.__class__.__name__, 'config': layer_config(layer.layer)})
+    elif isinstance(layer, L.RepeatVector):      # keras 2.2.4 layers/core.py
+        cfg.update(n=layer.n)
+    elif isinstance(layer, L.Permute):
+        cfg.update(dims=list(layer.dims))
+    elif isinstance(layer, L.Cropping1D):        # keras 2.2.4 layers/convolutional.py: the pair, as a list in JSON
+        cfg.update(cropping=list(layer.cropping))
+    elif isinstance(layer, L.ZeroPadding1D):
+        cfg.update(padding=list(layer.padding))
     # custom layers (MyLayer, bbhMahoGANy.py:164-188, defines no get_config): base config only, like Keras writes for them
     return cfg
 
@@ -395,6 +405,19 @@ def _layer_from_config(class_name, cfg, custom_objects):
         if inner['class_name'] not in ('LSTM', 'GRU', 'SimpleRNN'):
             raise ValueError('Bidirectional wraps an LSTM or a GRU, or a SimpleRNN, not %s' % inner['class_name'])
         return L.Bidirectional(_layer_from_config(inner['class_name'], inner['config'], None), merge_mode=cfg.get('merge_mode', 'concat'), **kw)
+    if class_name == 'TimeDistributed':          # the inner layer through its own path above; the wrapper refuses what is not a Dense, naming it
+        inner = cfg['layer']
+        return L.TimeDistributed(_layer_from_config(inner['class_name'], inner['config'], None), **kw)
+    if class_name == 'RepeatVector':
+        return L.RepeatVector(cfg['n'], **kw)
+    if class_name == 'Permute':
+        return L.Permute(tuple(cfg['dims']), **kw)
+    if class_name == 'Cropping1D':
+        c = cfg.get('cropping', (1, 1))
+        return L.Cropping1D(cropping=tuple(c) if isinstance(c, list) else c, **kw)
+    if class_name == 'ZeroPadding1D':
+        p = cfg.get('padding', 1)
+        return L.ZeroPadding1D(padding=tuple(p) if isinstance(p, list) else p, **kw)
     raise ValueError('Unknown layer: %s (pass it through custom_objects={%r: ...})' % (class_name, class_name))
 
 

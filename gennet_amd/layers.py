@@ -190,17 +190,30 @@ _ConvTape = collections.namedtuple('_ConvTape', 'x y act mask rate w run pl in_s
 
 
 class Dense(Layer):
-    """bbhMahoGANy.py:234 (100 -> 256*n_pix/2, MFMA GEMM), :377,:399,:494 (flatten -> 1 heads, streaming dot product)."""
-    fusable_act = True
+    """bbhMahoGANy.py:234 (100 -> 256*n_pix/2, MFMA GEMM), :377,:399,:494 (flatten -> 1 heads, streaming dot product).
+
+    On an input of rank 3 or more (batch axis included) the layer acts on the last axis, as in keras: kernel (input_shape[-1], units), output
+    input_shape[:-1] + (units,).  It then runs as the one-tap Conv1D it is, on the (B, positions, features) view and on that layer's kernels in
+    all three directions: their weight gradients split a long row axis, gn_dense_bwd's do not.  The planner's fusions of the
+    (batch, features) layer are switched off for such an instance: each was written against the rank-2 entry points."""
+
+    @property
+    def per_position(self):
+        """built on an input with axes in front of the features: the layer runs on the (B, positions, features) view"""
+        return getattr(self, '_per_position', False)
+
+    @property
+    def fusable_act(self):
+        return not self.per_position
 
     @property
     def offers_act_bwd(self):
-        return not _is_softmax(self)
+        return not _is_softmax(self) and not self.per_position
 
     @property
     def can_absorb_prev_act_bwd(self):
         k = getattr(self, 'kernel', None)          # the fused small-output backward needs an input width that is a multiple of 4
-        return self.units <= 4 and (k is None or k.shape[0] % 4 == 0)
+        return self.units <= 4 and (k is None or k.shape[0] % 4 == 0) and not self.per_position
 
     def __init__(self, units, activation=None, kernel_initializer='glorot_uniform', use_bias=True, kernel_regularizer=None, bias_regularizer=None,
                  activity_regularizer=None, **kw):
@@ -212,15 +225,47 @@ class Dense(Layer):
         self.units = int(units)
         self.activation = _act_spec(activation, 'Dense')
 
-    def build(self, input_shape):
-        assert len(input_shape) == 1, 'Dense expects (batch, features); Flatten first'
-        self.kernel = self.add_weight('kernel', glorot_uniform((input_shape[0], self.units)), regularizer=self.kernel_regularizer)
-        self.bias = self.add_weight('bias', np.zeros(self.units, np.float32), regularizer=self.bias_regularizer)
+    def build(self, input_shape, owner=None):
+        """owner: the wrapper (TimeDistributed) that holds the two weights, under its own name, in this layer's place"""
+        if len(input_shape) < 1:
+            raise ValueError('Dense expects (batch, ..., features), got a tensor without a feature axis')
+        self._per_position = len(input_shape) > 1
+        owner = self if owner is None else owner
+        self.kernel = owner.add_weight('kernel', glorot_uniform((input_shape[-1], self.units)), regularizer=self.kernel_regularizer)
+        self.bias = owner.add_weight('bias', np.zeros(self.units, np.float32), regularizer=self.bias_regularizer)
 
     def compute_output_shape(self, input_shape):
-        return (self.units,)
+        return tuple(input_shape[:-1]) + (self.units,)
+
+    def _forward_positions(self, ctx, node, x):
+        """Conv1D(units, 1) on the (B, positions, features) view: the kernel (features, units) is that layer's (1, features, units) in memory"""
+        a = self.activation
+        assert node.fused_act is None and node.fused_drop is None and node.fuse_prev < 0, 'a planner fusion on a per-position Dense'
+        ka = _kernel_act(a)
+        n_in = self.kernel.shape[0]
+        x3 = x.contiguous().view(x.shape[0], -1, n_in)
+        any_channels = ops.conv_layer_needs_any(n_in, self.units)
+        y = ops.conv1d_fwd(x3, self.kernel.data.view(1, n_in, self.units), self.bias.data, 1, 0, x3.shape[1], ka[0], ka[1], any_channels=any_channels)
+        if a is _SOFTMAX:
+            y = _channel_softmax(self, y)
+        if ctx.training:
+            ctx.tape[node.index] = (x3, y, a, any_channels, tuple(x.shape))
+        return y.view(tuple(x.shape[:-1]) + (self.units,))
+
+    def _backward_positions(self, ctx, node, dy, need_dx, need_dw):
+        x3, y, a, any_channels, x_shape = ctx.tape.pop(node.index)
+        n_in = self.kernel.shape[0]
+        dy = _conv_bwd_epilogue(dy.contiguous().view(y.shape), y, a, None, 0.0, ctx, node)
+        if need_dw:
+            ops.conv1d_wgrad(x3, dy, 1, 1, 0, self.kernel.grad.view(1, n_in, self.units), self.bias.grad, any_channels=any_channels)
+        if not need_dx:
+            return None
+        wt = ops.conv1d_transpose_w(self.kernel.data.view(1, n_in, self.units))
+        return ops.conv1d_dgrad(dy, wt, x3.shape[1], 1, 0, None, any_channels=any_channels).view(x_shape)
 
     def forward(self, ctx, node, x):
+        if self.per_position:
+            return self._forward_positions(ctx, node, x)
         a = node.fused_act or self.activation
         ka = _kernel_act(a)
         y = ops.dense_fwd(x, self.kernel.data, self.bias.data, ka[0], ka[1])
@@ -235,6 +280,9 @@ class Dense(Layer):
         return _epilogue_writes_dy(self, node)
 
     def backward(self, ctx, node, dy, need_dx, need_dw, prev=None):
+        if self.per_position:
+            assert prev is None
+            return self._backward_positions(ctx, node, dy, need_dx, need_dw)
         x, y, a = ctx.tape.pop(node.index)
         dy = _conv_bwd_epilogue(dy.contiguous(), y, a, None, 0.0, ctx, node)
         if prev is not None:
@@ -1511,3 +1559,7 @@ from .recurrent import GRU, LSTM, Bidirectional, SimpleRNN  # noqa: E402,F401
 
 # keras.layers.SeparableConv1D lives in gennet_amd/separable.py and is part of this name space
 from .separable import SeparableConv1D  # noqa: E402,F401
+
+# keras.layers.TimeDistributed, RepeatVector, Permute, Cropping1D and ZeroPadding1D live in gennet_amd/sequence.py and are part of
+# this name space
+from .sequence import Cropping1D, Permute, RepeatVector, TimeDistributed, ZeroPadding1D  # noqa: E402,F401

@@ -1218,6 +1218,61 @@ def dilate_merge(xs, B, d, off, L, out=None):
     return x
 
 
+# ---------------------------------------------------------------------------------------------- sequence plumbing (csrc/sequence.hip)
+def permute(x, perm, out=None):
+    """x.permute(perm).contiguous() for 2 .. 4 axes (perm counts the batch axis, axis 0): a copy, a row copy or a tiled transposition.  The backward
+    is the same call with the inverse permutation."""
+    _chk(x, out)
+    perm = [int(v) for v in perm]
+    R = x.dim()
+    if len(perm) != R:
+        raise ValueError('permute: %d axes for a tensor of %d' % (len(perm), R))
+    if sorted(perm) != list(range(R)):
+        raise ValueError('permute: %r is no permutation of 0 .. %d' % (perm, R - 1))
+    shape = tuple(int(x.shape[p]) for p in perm)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(y.shape) == shape
+    _lib.call('gn_permute', _p(x), _p(y), (ctypes.c_int * R)(*[int(v) for v in x.shape]), (ctypes.c_int * R)(*perm), R, _stream())
+    return y
+
+
+def repeat_fwd(x, n, out=None):
+    """x (B, C) -> (B, n, C), every row n times (keras RepeatVector)."""
+    _chk(x, out)
+    B, C = (int(v) for v in x.shape)
+    n = int(n)
+    y = torch.empty((B, n, C), dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(y.shape) == (B, n, C)
+    _lib.call('gn_repeat_fwd', _p(x), _p(y), B, n, C, _stream())
+    return y
+
+
+def repeat_bwd(dy, out=None):
+    """dy (B, n, C) -> dx (B, C) = the sum over n, accumulated in fp64 in a fixed order (by the shape alone) and rounded once."""
+    _chk(dy, out)
+    B, n, C = (int(v) for v in dy.shape)
+    dx = torch.empty((B, C), dtype=torch.float32, device=dy.device) if out is None else out
+    assert tuple(dx.shape) == (B, C)
+    nb = _lib.size('gn_repeat_bwd_workspace', B, n, C)
+    ws = workspace(nb, dy.device) if nb else None
+    _lib.call('gn_repeat_bwd', _p(dy), _p(dx), _p(ws), ws.numel() if nb else 0, B, n, C, _stream())
+    return dx
+
+
+def shift1d(x, offset, Lout, out=None):
+    """x (B, Lin, C) -> y (B, Lout, C), y[b, l] = x[b, l - offset] inside [0, Lin), +0 elsewhere: ZeroPadding1D with offset = left and
+    Lout = left + Lin + right, Cropping1D with offset = -left and Lout = Lin - left - right; each is the other's backward."""
+    _chk(x, out)
+    B, Lin, C = (int(v) for v in x.shape)
+    offset, Lout = int(offset), int(Lout)
+    if Lout < 1:
+        raise ValueError('shift1d: Lout %d must be >= 1' % Lout)
+    y = torch.empty((B, Lout, C), dtype=torch.float32, device=x.device) if out is None else out
+    assert tuple(y.shape) == (B, Lout, C)
+    _lib.call('gn_shift1d', _p(x), _p(y), B, Lin, Lout, C, offset, _stream())
+    return y
+
+
 # ---------------------------------------------------------------------------------------------- batch norm
 def bn_stats(x2d):
     """x2d: (rows, C) view.  Returns fp64 sums tensor (2*C,): [sum x | sum x^2]."""

@@ -567,6 +567,28 @@ int gn_dwconv1d_dgrad(const float* dy, const float* w, float* dx, int B, int L, 
 int gn_dwconv1d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int B, int L, int C, int k, int dm, int stride, int dilation,
                       int pad_left, int Lout, void* stream);
 
+/* ---- sequence plumbing (csrc/sequence.hip; keras layers.Permute, RepeatVector, Cropping1D, ZeroPadding1D).  Contiguous fp32, out of
+ * place, memory-bound passes; no atomics, no host synchronisation; float4 units where the inner extent is a multiple of 4 and both tensors are
+ * 16-byte aligned, else floats.
+ *   gn_permute: axis i of y is axis perm[i] of x, for R = 2 .. 4 axes (the batch axis is axis 0); extents are x's.  extents_host and perm_host are
+ *     HOST arrays of R ints, read when the entry point runs.  Axes of extent 1 are dropped and axes that stay adjacent and in order merged; then a
+ *     device-to-device copy (nothing left to permute), a row copy (the innermost axis stays innermost) or a tiled transposition through LDS (it
+ *     changes), batched over the remaining axes.  The backward of a permutation is this entry with the inverse permutation.
+ *   gn_repeat_fwd: x (B, C) -> y (B, n, C), y[b, j, :] = x[b, :].
+ *   gn_repeat_bwd: dy (B, n, C) -> dx (B, C), dx[b, c] = sum_j dy[b, j, c] in fp64, j ascending, rounded once; where B C is small and n large j is cut
+ *     into chunks, by (B, n, C) alone, whose fp64 partial sums are added in ascending order: bit-identical from run to run.
+ *     ws: gn_repeat_bwd_workspace(B, n, C) bytes, 8-byte aligned (0 bytes: ws may be NULL).
+ *   gn_shift1d: x (B, Lin, C) -> y (B, Lout, C), y[b, l, :] = x[b, l - offset, :] where 0 <= l - offset < Lin, +0.0f elsewhere.  ZeroPadding1D is
+ *     offset = left, Lout = left + Lin + right; Cropping1D offset = -left, Lout = Lin - left - right; the backward of each is the other's forward.
+ * GN_EINVAL, nothing launched: a NULL pointer (except ws as above), y == x, R outside 2 .. 4, a perm that is no permutation of 0 .. R - 1, a negative
+ * extent, 2^61 elements or more, a merged axis of 2^31 elements or more, B < 0, any of n, C, Lin, Lout < 1, n C >= 2^31; GN_EWORKSPACE: ws too
+ * small.  An extent of 0 / B == 0 is GN_OK without a launch. */
+int gn_permute(const float* x, float* y, const int* extents_host, const int* perm_host, int R, void* stream);
+int gn_repeat_fwd(const float* x, float* y, int B, int n, int C, void* stream);
+size_t gn_repeat_bwd_workspace(int B, int n, int C);
+int gn_repeat_bwd(const float* dy, float* dx, void* ws, size_t ws_bytes, int B, int n, int C, void* stream);
+int gn_shift1d(const float* x, float* y, int B, int Lin, int Lout, int C, int offset, void* stream);
+
 /* ---- losses + metric (compile(loss='binary_crossentropy'|'mean_squared_error', metrics=['accuracy']),
  *      bbhMahoGANy.py:1101-1119) ---------------------------------------------------------------------------
  * p, y: (B, 1).  out[0] = loss (mean over the local B rows scaled by B/Bglobal), out[1] = #rows with round(p)==y;
