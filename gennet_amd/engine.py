@@ -86,7 +86,7 @@ class Param(object):
         self.name = name
         self.regularizer = regularizer     # a regularizers.L1L2 or None: its penalty enters the loss of every model that holds the weight
         self.shape = tuple(value.shape)
-        self._host = np.ascontiguousarray(value, np.float32)
+        self._host = np.ascontiguousarray(value, np.float32).reshape(self.shape)      # ascontiguousarray makes a () value (1,)
         self._data = None
         self.grad = None
         self.trainable = trainable
@@ -110,6 +110,8 @@ class Param(object):
 
     def assign(self, w):
         w = np.ascontiguousarray(w, np.float32)
+        if self.shape == () and w.size == 1:
+            w = w.reshape(())
         assert tuple(w.shape) == self.shape, '%s: %s vs %s' % (self.name, w.shape, self.shape)
         if self._data is None:
             self._host = w

@@ -17,6 +17,7 @@
     from gennet_amd.keras.layers.wrappers import TimeDistributed       # over Dense; also gennet_amd.keras.layers.TimeDistributed
     from gennet_amd.keras.layers.core import RepeatVector, Permute     # also gennet_amd.keras.layers.RepeatVector, .Permute
     from gennet_amd.keras.layers.convolutional import Cropping1D, ZeroPadding1D   # also gennet_amd.keras.layers.Cropping1D, .ZeroPadding1D
+    from gennet_amd.keras.layers.dense_attention import Attention      # tf.keras 2.x; also gennet_amd.keras.layers.Attention
     from gennet_amd.keras.engine.topology import Layer
     from gennet_amd.keras.optimizers import Adam, SGD, RMSprop, Adagrad, Adadelta, Adamax   # Nadam: placeholder
     from gennet_amd.keras import backend as K
@@ -77,10 +78,11 @@ _merge = _pick(_layers, 'Add', 'Subtract', 'Multiply', 'Average', 'Maximum', 'Mi
                'add', 'subtract', 'multiply', 'average', 'maximum', 'minimum', 'concatenate', 'dot')
 _recurrent = _pick(_layers, 'LSTM', 'GRU', 'SimpleRNN')
 _wrappers = _pick(_layers, 'Bidirectional', 'TimeDistributed')
+_attention = _pick(_layers, 'Attention')
 _top = dict(_pick(_engine, 'Input'), **_pick(_layers, 'MyLayer'))
 _top['GlobalAveragePooling1D'] = _pooling_placeholder('GlobalAveragePooling1D', '33-34')
 _top.update(_pick(_layers, 'AveragePooling2D', 'GlobalAveragePooling2D', 'GlobalMaxPooling1D', 'GlobalMaxPooling2D'))
-for _d in (_core, _norm, _conv, _act, _noise, _merge, _recurrent, _wrappers):
+for _d in (_core, _norm, _conv, _act, _noise, _merge, _recurrent, _wrappers, _attention):
     _top.update((k, v) for k, v in _d.items() if v is _layers.__dict__.get(k))
 
 _TREE = {
@@ -100,6 +102,7 @@ _TREE = {
     'layers.merge': _merge,
     'layers.recurrent': _recurrent,
     'layers.wrappers': _wrappers,
+    'layers.dense_attention': _attention,
     'losses': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if k != 'categorical_accuracy'),
     'metrics': dict((k, v) for k, v in _engine.LOSS_FUNCTIONS.items() if _engine._loss_name(v) in _engine.PASS_METRICS),
 }

@@ -126,7 +126,7 @@ def save_weights_to_group(g, layers):
             raise ValueError('layer %s has duplicate weight names' % l.name)
         lg.attrs['weight_names'] = np.array([n.encode('utf-8') for n in names], dtype='S') if names else np.zeros((0,), np.float64)
         for p, n in zip(ws, names):
-            lg.create_dataset(n, np.ascontiguousarray(p.numpy(), dtype=np.float32))
+            lg.create_dataset(n, np.ascontiguousarray(p.numpy(), dtype=np.float32).reshape(p.shape))      # a () weight stays ()
 
 
 def _decode_list(a):
@@ -231,6 +231,8 @@ def layer_config(layer):
         cfg.update(axis=layer.axis)
     elif isinstance(layer, L.Dot):               # axes as keras writes it: the int, or the pair as a list
         cfg.update(axes=layer.axes if isinstance(layer.axes, int) else list(layer.axes), normalize=layer.normalize)
+    elif isinstance(layer, L.Attention):         # tf.keras 2.x layers/dense_attention.py: BaseDenseAttention writes causal and dropout, Attention use_scale
+        cfg.update(use_scale=layer.use_scale, causal=layer.causal, dropout=0.0)
     elif isinstance(layer, (L.LSTM, L.GRU, L.SimpleRNN)):    # the keys of keras 2.2.4 layers/recurrent.py LSTM / GRU / SimpleRNN.get_config
         cfg.update(return_sequences=layer.return_sequences, return_state=False, go_backwards=layer.go_backwards, stateful=False, unroll=layer.unroll,
                    units=layer.units, activation=layer.activation, use_bias=True,
@@ -383,6 +385,8 @@ def _layer_from_config(class_name, cfg, custom_objects):
         return L.Concatenate(axis=cfg.get('axis', -1), **kw)
     if class_name == 'Dot':
         return L.Dot(axes=cfg['axes'], normalize=cfg.get('normalize', False), **kw)
+    if class_name == 'Attention':                # dtype is accepted and ignored; the layer refuses a dropout other than 0 by name
+        return L.Attention(use_scale=cfg.get('use_scale', False), causal=cfg.get('causal', False), dropout=cfg.get('dropout', 0.0), **kw)
     if class_name in ('LSTM', 'GRU'):            # the layer itself refuses what it does not run, naming the key
         keys = ('activation', 'recurrent_activation', 'use_bias', 'kernel_initializer', 'recurrent_initializer', 'bias_initializer',
                 'unit_forget_bias' if class_name == 'LSTM' else 'reset_after',

@@ -1563,3 +1563,6 @@ from .separable import SeparableConv1D  # noqa: E402,F401
 # keras.layers.TimeDistributed, RepeatVector, Permute, Cropping1D and ZeroPadding1D live in gennet_amd/sequence.py and are part of
 # this name space
 from .sequence import Cropping1D, Permute, RepeatVector, TimeDistributed, ZeroPadding1D  # noqa: E402,F401
+
+# keras.layers.Attention lives in gennet_amd/attention.py and is part of this name space
+from .attention import Attention  # noqa: E402,F401

@@ -538,6 +538,53 @@ def l2norm_bwd(dy, y, inv, view, out=None):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- fused attention (csrc/attention.hip)
+ATTENTION_BQ, ATTENTION_BK, ATTENTION_MAX_D = (_lib.CONSTS[_k] for _k in ('GN_ATTN_BQ', 'GN_ATTN_BK', 'GN_ATTN_MAX_D'))
+
+
+def _attention_shape(what, q, k, v, scale):
+    _chk(q, k, v, scale)
+    if not (q.dim() == k.dim() == v.dim() == 3) or any(t.dtype != torch.float32 for t in (q, k, v)) or q.shape[0] != k.shape[0] or k.shape[:2] != v.shape[:2] \
+            or q.shape[2] != k.shape[2]:
+        raise ValueError('%s: float32 q (B, Tq, d), k (B, Tk, d), v (B, Tk, dv) are expected, got %r, %r, %r' % (what, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if scale is not None and (scale.numel() != 1 or scale.dtype != torch.float32):
+        raise ValueError('%s: scale is one float32 on the device, got %r' % (what, tuple(scale.shape)))
+    return int(q.shape[0]), int(q.shape[1]), int(k.shape[1]), int(q.shape[2]), int(v.shape[2])
+
+
+def attention_fwd(q, k, v, scale=None, causal=False, training=False, out=None):
+    """-> (out, lse): out (B, Tq, dv) = softmax_j(scale * q . k^T) . v over q (B, Tq, d), k (B, Tk, d), v (B, Tk, dv) in one launch, no (Tq, Tk) tensor
+    in memory; under `causal` over j <= i only.  scale: a one-element device tensor (read by the kernel, so a captured step replays with the
+    updated weight) or None for 1.  lse (B, Tq) = row maximum + log(row sum) in the training phase, else None."""
+    B, Tq, Tk, d, dv = _attention_shape('attention_fwd', q, k, v, scale)
+    _chk(out)
+    if out is None:
+        out = torch.empty((B, Tq, dv), dtype=torch.float32, device=q.device)
+    assert out.numel() == B * Tq * dv
+    lse = torch.empty((B, Tq), dtype=torch.float32, device=q.device) if training else None
+    _lib.call('gn_attention_fwd', _p(q), _p(k), _p(v), _p(scale), _p(out), _p(lse), B, Tq, Tk, d, dv, 1 if causal else 0, _stream())
+    return out, lse
+
+
+def attention_bwd(q, k, v, out, lse, dout, scale=None, causal=False, need=(True, True, True), need_dscale=False):
+    """-> (dq, dk, dv, dscale_rows) from the forward's operands, out and lse and the gradient dout (B, Tq, dv): each of dq, dk, dv where `need` asks
+    (else None), and with need_dscale the (B * Tq,) row partials of the gradient of scale, sum_j dS[i, j] (q_i . k_j), whose sum (ops.bias_grad over
+    the (B * Tq, 1) view) is the gradient.  p is recomputed from lse tile by tile; no atomics."""
+    B, Tq, Tk, d, dv = _attention_shape('attention_bwd', q, k, v, scale)
+    _chk(out, lse, dout)
+    if tuple(out.shape) != (B, Tq, dv) or dout.numel() != out.numel() or lse.numel() != B * Tq:
+        raise ValueError('attention_bwd: out, dout (B, Tq, dv) and lse (B, Tq) are expected, got %r, %r, %r' % (tuple(out.shape), tuple(dout.shape), tuple(lse.shape)))
+    dq = torch.empty_like(q) if need[0] else None
+    dk = torch.empty_like(k) if need[1] else None
+    dvv = torch.empty_like(v) if need[2] else None
+    rows = torch.empty((B * Tq,), dtype=torch.float32, device=q.device) if need_dscale else None
+    nbytes = _lib.size('gn_attention_workspace', B, Tq)
+    ws = workspace(nbytes, q.device)
+    _lib.call('gn_attention_bwd', _p(q), _p(k), _p(v), _p(scale), _p(out), _p(lse), _p(dout), _p(dq), _p(dk), _p(dvv), _p(rows), _p(ws), ws.numel(), B, Tq,
+              Tk, d, dv, 1 if causal else 0, _stream())
+    return dq, dk, dvv, rows
+
+
 # ---------------------------------------------------------------------------------------------- LSTM recurrence (csrc/lstm.hip, DESIGN 8o)
 LSTM_ACT = _lib.enum_members('GN_LSTM_')                        # enum gn_lstm_act: {'tanh': 0, 'sigmoid': 1, 'relu': 2, 'linear': 3, 'hard_sigmoid': 4}
 

@@ -423,6 +423,31 @@ int gn_bmm_valu(const float* a, const float* b, float* c, int batch, int M, int 
 int gn_l2norm_fwd(const float* x, float* y, float* inv, size_t outer, int P, int inner, void* stream);
 int gn_l2norm_bwd(const float* dy, const float* y, const float* inv, float* dx, size_t outer, int P, int inner, void* stream);
 
+/* ---- fused dot-product attention (csrc/attention.hip; tf.keras layers.Attention) over contiguous fp32 q (B, Tq, d), k (B, Tk, d),
+ * v (B, Tk, dv):   s[i, j] = scale * sum_c q[i, c] k[j, c],   p = softmax_j(s),   out[i, :] = sum_j p[i, j] v[j, :]     out (B, Tq, dv).
+ * `causal`: entry (i, j) takes part iff j <= i (the lower triangle of the (Tq, Tk) matrix; Tq != Tk allowed); a masked entry is exactly 0 in the row
+ * sum and in every gradient, and tiles wholly above the diagonal are not visited.  `scale` is a DEVICE pointer to one float, NULL for 1: a captured
+ * step replays with the updated value.  No (Tq, Tk) tensor is written: a block owns GN_ATTN_BQ rows of one batch entry and walks the other side in
+ * ascending tiles of GN_ATTN_BK rows on v_mfma_f32_32x32x2_f32 with a running maximum and sum.  No atomics; a row's result does not depend on B, on
+ * the launch or on the grid, and two runs give identical bits.  Any B, Tq, Tk >= 1; 1 <= d, dv <= GN_ATTN_MAX_D; 4-byte aligned pointers (16-byte
+ * loads where a base pointer is 16-byte aligned and its row length a multiple of 4).
+ * gn_attention_fwd: writes out and, where lse is not NULL (the training phase), lse (B, Tq) = row maximum + log(row sum).
+ * gn_attention_bwd: from q, k, v, scale, out and lse as the forward left them and dout (B, Tq, dv), writes each of dq (B, Tq, d), dk (B, Tk, d),
+ *   dv_out (B, Tk, dv) that is not NULL, and into dscale_rows (B Tq floats, may be NULL) one partial per query row of the gradient of `scale`,
+ *   sum_j dS[i, j] (q_i . k_j): their sum is the gradient (gn_bias_grad over the (B Tq, 1) view).  p = expf(s - lse) is recomputed tile by tile.
+ *   ws: gn_attention_workspace(B, Tq) bytes (delta[i] = sum_c dout[i, c] out[i, c]).
+ * GN_EINVAL, nothing launched: a NULL pointer, B < 0, Tq or Tk < 1, d or dv outside 1 .. GN_ATTN_MAX_D, more than 2^31 - 1 blocks;
+ * GN_EWORKSPACE: ws too small.  B == 0 (and a backward with no gradient asked for) is GN_OK without a launch. */
+#define GN_ATTN_BQ 128
+#define GN_ATTN_BK 64
+#define GN_ATTN_MAX_D 128
+size_t gn_attention_workspace(int B, int Tq);
+int gn_attention_fwd(const float* q, const float* k, const float* v, const float* scale, float* out, float* lse, int B, int Tq, int Tk, int d, int dv,
+                     int causal, void* stream);
+int gn_attention_bwd(const float* q, const float* k, const float* v, const float* scale, const float* out, const float* lse, const float* dout, float* dq,
+                     float* dk, float* dv_out, float* dscale_rows, void* ws, size_t ws_bytes, int B, int Tq, int Tk, int d, int dv, int causal,
+                     void* stream);
+
 /* ---- LSTM recurrence (csrc/lstm.hip; keras layers.LSTM, LSTMCell of keras 2.2.4).  Gate columns i, f, c, o of width u:
  *   z_t = zx_t + h_{t-1} . U + b;  i = ra(z_i), f = ra(z_f), g = act(z_c), o = ra(z_o);  c_t = f c_{t-1} + i g;  h_t = o act(c_t)
  * with act one of GN_LSTM_TANH, _SIGMOID, _RELU, _LINEAR and ra one of GN_LSTM_HARD_SIGMOID (min(max(0.2 x + 0.5, 0), 1)), GN_LSTM_SIGMOID.
