@@ -4,6 +4,7 @@
     from gennet_amd.keras.layers import Dense, Input, Reshape, Dropout
     from gennet_amd.keras.layers.core import Activation, Flatten
     from gennet_amd.keras.layers.normalization import BatchNormalization
+    from gennet_amd.keras.layers.normalization import LayerNormalization   # tf.keras 2.x; also gennet_amd.keras.layers.LayerNormalization
     from gennet_amd.keras.layers.convolutional import UpSampling1D, Conv2D, Conv1D, Conv2DTranspose
     from gennet_amd.keras.layers.convolutional import SeparableConv1D  # also gennet_amd.keras.layers.SeparableConv1D
     from gennet_amd.keras.layers.advanced_activations import LeakyReLU, ReLU, Softmax
@@ -66,7 +67,7 @@ def _pick(mod, *names):
 
 
 _core = _pick(_layers, 'Activation', 'ActivityRegularization', 'Dense', 'Dropout', 'Flatten', 'Reshape', 'RepeatVector', 'Permute')
-_norm = _pick(_layers, 'BatchNormalization')
+_norm = _pick(_layers, 'BatchNormalization', 'LayerNormalization')
 _conv = dict(_pick(_layers, 'Conv1D', 'Conv2D', 'Conv2DTranspose', 'SeparableConv1D', 'UpSampling1D', 'MaxPooling2D', 'Cropping1D', 'ZeroPadding1D'),
              **_unused('37-38', 'UpSampling2D'))
 _conv.update((n, _pooling_placeholder(n, '37-38')) for n in ('AveragePooling1D', 'MaxPooling1D'))

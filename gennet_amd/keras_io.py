@@ -199,6 +199,10 @@ def layer_config(layer):
         cfg.update(axis=layer.axis, momentum=layer.momentum, epsilon=layer.epsilon, center=True, scale=True, beta_initializer=_ZEROS, gamma_initializer=_ONES,
                    moving_mean_initializer=_ZEROS, moving_variance_initializer=_ONES, beta_regularizer=_reg(layer.beta_regularizer), gamma_regularizer=_reg(layer.gamma_regularizer),
                    beta_constraint=None, gamma_constraint=None)
+    elif isinstance(layer, L.LayerNormalization):      # tf.keras 2.x layers/normalization.py: axis is the list of non-negative axes after build
+        cfg.update(axis=list(layer.axis) if isinstance(layer.axis, list) else layer.axis, epsilon=layer.epsilon, center=layer.center, scale=layer.scale,
+                   beta_initializer=_ZEROS, gamma_initializer=_ONES, beta_regularizer=_reg(layer.beta_regularizer),
+                   gamma_regularizer=_reg(layer.gamma_regularizer), beta_constraint=None, gamma_constraint=None)
     elif isinstance(layer, L.PReLU):
         cfg.update(alpha_initializer=_ZEROS, alpha_regularizer=_reg(layer.alpha_regularizer), alpha_constraint=None, shared_axes=None)
     elif isinstance(layer, L.LeakyReLU):
@@ -347,6 +351,10 @@ def _layer_from_config(class_name, cfg, custom_objects):
     if class_name == 'BatchNormalization':
         return L.BatchNormalization(axis=cfg.get('axis', -1), momentum=cfg.get('momentum', 0.99), epsilon=cfg.get('epsilon', 1e-3),
                                     **regs('beta_regularizer', 'gamma_regularizer'), **kw)
+    if class_name == 'LayerNormalization':       # dtype is accepted and ignored; the layer refuses initializers and constraints it does not run, by name
+        keys = ('beta_initializer', 'gamma_initializer', 'beta_constraint', 'gamma_constraint')
+        return L.LayerNormalization(axis=cfg.get('axis', -1), epsilon=cfg.get('epsilon', 1e-3), center=cfg.get('center', True), scale=cfg.get('scale', True),
+                                    **dict((k, cfg[k]) for k in keys if k in cfg), **regs('beta_regularizer', 'gamma_regularizer'), **kw)
     if class_name == 'PReLU':
         return L.PReLU(alpha_initializer=cfg.get('alpha_initializer', 'zeros'), shared_axes=cfg.get('shared_axes'), **regs('alpha_regularizer'), **kw)
     if class_name == 'LeakyReLU':

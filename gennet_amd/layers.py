@@ -1566,3 +1566,6 @@ from .sequence import Cropping1D, Permute, RepeatVector, TimeDistributed, ZeroPa
 
 # keras.layers.Attention lives in gennet_amd/attention.py and is part of this name space
 from .attention import Attention  # noqa: E402,F401
+
+# keras.layers.LayerNormalization lives in gennet_amd/layernorm.py and is part of this name space
+from .layernorm import LayerNormalization  # noqa: E402,F401

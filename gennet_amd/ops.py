@@ -585,6 +585,53 @@ def attention_bwd(q, k, v, out, lse, dout, scale=None, causal=False, need=(True,
     return dq, dk, dvv, rows
 
 
+# ---------------------------------------------------------------------------------------------- layer normalisation (csrc/layernorm.hip)
+LAYERNORM_ROWS_MAX_N, LAYERNORM_BLOCK_MAX_N, LAYERNORM_FWD_GRID_CAP, LAYERNORM_BWD_GRID_CAP, LAYERNORM_BWD_GRID_CAP_WIDE = (
+    _lib.CONSTS[_k] for _k in ('GN_LN_ROWS_MAX_N', 'GN_LN_BLOCK_MAX_N', 'GN_LN_FWD_GRID_CAP', 'GN_LN_BWD_GRID_CAP', 'GN_LN_BWD_GRID_CAP_WIDE'))
+
+
+def _layernorm_rows(what, x, N, *params):
+    """rows of the (rows, N) view of x: its trailing axes hold N contiguous floats; every parameter vector has N"""
+    if x.dtype != torch.float32 or N < 1 or x.numel() == 0 or x.numel() % N:
+        raise ValueError('%s: a non-empty float32 tensor whose trailing axes hold N = %d values is expected, got %r' % (what, N, tuple(x.shape)))
+    for p in params:
+        if p is not None and (p.dtype != torch.float32 or p.numel() != N):
+            raise ValueError('%s: a parameter or its gradient holds %d values, N = %d' % (what, p.numel(), N))
+    return x.numel() // N
+
+
+def layernorm_fwd(x, gamma, beta, N, eps, training=False, out=None):
+    """-> (y, mean, rstd): y = (x - mean_r) * rstd_r * gamma + beta over the (rows, N) view of x (rows: every leading axis; N: the product of the
+    normalised trailing axes), one launch, biased variance from the centred second pass.  gamma / beta: (N,) device tensors, None for
+    scale=False / center=False.  mean and rstd (rows,) in the training phase, else None."""
+    _chk(x, gamma, beta, out)
+    rows = _layernorm_rows('layernorm_fwd', x, N, gamma, beta)
+    y = torch.empty_like(x) if out is None else out
+    assert y.numel() == x.numel()
+    mean = torch.empty((rows,), dtype=torch.float32, device=x.device) if training else None
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if training else None
+    _lib.call('gn_layernorm_fwd', _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, N, eps, _stream())
+    return y, mean, rstd
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, N, need_dx=True, dgamma=None, dbeta=None, need_dgamma=False, need_dbeta=False):
+    """-> (dx, dgamma, dbeta) from the forward's x, mean and rstd: dx where need_dx (else None); dgamma / dbeta (N,) into the tensors given, or
+    into new ones where need_dgamma / need_dbeta, else None -- both None is a frozen layer: one launch, no partials.  One launch over the
+    elements plus the fixed-order fp64 sum of the per-block partials; no atomics."""
+    _chk(dy, x, gamma, mean, rstd, dgamma, dbeta)
+    rows = _layernorm_rows('layernorm_bwd', x, N, gamma, dgamma, dbeta)
+    if dy.numel() != x.numel() or dy.dtype != torch.float32 or mean.numel() != rows or rstd.numel() != rows:
+        raise ValueError('layernorm_bwd: dy like x and mean, rstd of %d rows are expected, got %r, %r, %r' % (rows, tuple(dy.shape), tuple(mean.shape), tuple(rstd.shape)))
+    dx = torch.empty_like(x) if need_dx else None
+    if dgamma is None and need_dgamma:
+        dgamma = torch.empty((N,), dtype=torch.float32, device=x.device)
+    if dbeta is None and need_dbeta:
+        dbeta = torch.empty((N,), dtype=torch.float32, device=x.device)
+    ws = workspace(_lib.size('gn_layernorm_bwd_workspace', rows, N), x.device)
+    _lib.call('gn_layernorm_bwd', _p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), _p(ws), ws.numel(), rows, N, _stream())
+    return dx, dgamma, dbeta
+
+
 # ---------------------------------------------------------------------------------------------- LSTM recurrence (csrc/lstm.hip, DESIGN 8o)
 LSTM_ACT = _lib.enum_members('GN_LSTM_')                        # enum gn_lstm_act: {'tanh': 0, 'sigmoid': 1, 'relu': 2, 'linear': 3, 'hard_sigmoid': 4}
 

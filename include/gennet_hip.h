@@ -448,6 +448,38 @@ int gn_attention_bwd(const float* q, const float* k, const float* v, const float
                      float* dk, float* dv_out, float* dscale_rows, void* ws, size_t ws_bytes, int B, int Tq, int Tk, int d, int dv, int causal,
                      void* stream);
 
+/* ---- layer normalisation over the trailing axes (csrc/layernorm.hip; keras layers.LayerNormalization) on the contiguous fp32 (rows, N)
+ * view, rows the batch and every leading axis, N the product of the normalised axes:
+ *   mean_r = sum_c x / N,  var_r = sum_c (x - mean_r)^2 / N (biased),  rstd_r = 1 / sqrt(var_r + eps),  xhat = (x - mean_r) rstd_r,
+ *   y = xhat gamma[c] + beta[c];   g = dy gamma,  dx = rstd_r ((g - mean_c g) - xhat mean_c (g xhat)),  dgamma[c] = sum_r dy xhat,  dbeta[c] = sum_r dy.
+ * The variance is the centred second pass over the values of the first, never E[x^2] - E[x]^2.  Regimes by N alone: N <= GN_LN_ROWS_MAX_N a
+ * sub-group of min(64, pow2ceil(ceil(N / 4))) lanes owns a row in registers; N <= GN_LN_BLOCK_MAX_N a block of 256 lanes owns it in registers;
+ * beyond, a block streams it (the centred pass and the output pass read x again).  Bytes per element: 8 forward (+ 8 / N for mean and rstd) and
+ * 12 backward in the first two regimes, 16 and 20 streamed.  16-byte accesses where N % 4 == 0 and every pointer is 16-byte aligned, else 4-byte
+ * accesses of the same kernel: the same bits.  No atomics: fp32 reductions in an order fixed by N alone; the weight gradients leave each of the
+ * blocks (at most GN_LN_BWD_GRID_CAP, GN_LN_BWD_GRID_CAP_WIDE where N > GN_LN_ROWS_MAX_N) as one fp32 (2, N) partial in the workspace and are summed
+ * in fp64 in a fixed order over the blocks, rounded once.  A
+ * row's y and dx do not depend on rows, on the grid or on the launch; two runs give identical bits.  y may alias x, dx may alias dy.
+ * gn_layernorm_fwd: gamma NULL is scale=False (1), beta NULL is center=False (0); mean and rstd (rows floats each) are written where given -- the
+ *   training phase -- and are both NULL in the inference phase.
+ * gn_layernorm_bwd: from dy, x and the mean / rstd the forward wrote; each of dx, dgamma, dbeta is written where it is not NULL, in any
+ *   combination (scale=False with center=True asks for dbeta alone), except dgamma without gamma; all three NULL is GN_OK without a launch;
+ *   dgamma and dbeta both NULL (a frozen layer) writes no partials and launches no reduction.  ws: gn_layernorm_bwd_workspace(rows, N) bytes,
+ *   4-byte aligned; it may be NULL where dgamma and dbeta are and N <= GN_LN_BLOCK_MAX_N.
+ * GN_EINVAL, nothing launched: a required pointer NULL (forward x, y; backward dy, x, mean, rstd, and ws where needed), rows < 1, N < 1,
+ * rows * N >= 2^62, eps negative or not finite, mean without rstd or rstd without mean, dgamma without gamma, a misaligned workspace;
+ * GN_EWORKSPACE: ws_bytes below gn_layernorm_bwd_workspace (which is 0 for a shape the entry points refuse). */
+#define GN_LN_ROWS_MAX_N 1024
+#define GN_LN_BLOCK_MAX_N 4096
+#define GN_LN_FWD_GRID_CAP 2048
+#define GN_LN_BWD_GRID_CAP 1024
+#define GN_LN_BWD_GRID_CAP_WIDE 512
+int gn_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, size_t rows, int N, float eps,
+                     void* stream);
+size_t gn_layernorm_bwd_workspace(size_t rows, int N);
+int gn_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,
+                     void* ws, size_t ws_bytes, size_t rows, int N, void* stream);
+
 /* ---- LSTM recurrence (csrc/lstm.hip; keras layers.LSTM, LSTMCell of keras 2.2.4).  Gate columns i, f, c, o of width u:
  *   z_t = zx_t + h_{t-1} . U + b;  i = ra(z_i), f = ra(z_f), g = act(z_c), o = ra(z_o);  c_t = f c_{t-1} + i g;  h_t = o act(c_t)
  * with act one of GN_LSTM_TANH, _SIGMOID, _RELU, _LINEAR and ra one of GN_LSTM_HARD_SIGMOID (min(max(0.2 x + 0.5, 0), 1)), GN_LSTM_SIGMOID.
